@@ -29,6 +29,23 @@ reported beside it.  Multi-GPU: one process per GPU.
   --mode replica: each rank indexes its own copy of the workload (independent
       epochs; no data-path collective; weak scaling).
 LX_DIST_BACKEND=gloo (rehearsal only) lets several ranks share one GPU.
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does what the result
+line's headline needs and no more: it builds the workload, warms up, times the
+N index steps and the N ForklessCause steps, writes --dump-outputs if asked,
+and prints the line.  --full adds everything else the benchmark measures or
+checks: the host-side ForklessCause spot check, the power / clock samples, the
+per-call latency and level-fed legs, the QuorumIndexer line, the C1/C2/C4
+lines, the configs[4] abft and drop-in legs, the CPU baselines, and (N > 1 row
+segments) the column-shard leg; the --no-* options switch single legs of a
+--full run off.
+
+--dump-outputs DIR writes, after the timed steps, what the last timed steps
+left for a caller (rank 0 writes): the HighestBefore and LowestAfter rows of a
+fixed seeded sample of events (the batched getters, reference layouts, as
+u32 words) and a fixed seeded sample of the last ForklessCause step's answers,
+as DIR/<name>.npy.  The workload is seeded, so two runs with the same arguments
+see the same inputs and can be compared array for array.
 """
 
 import argparse
@@ -590,6 +607,40 @@ def power_probe(step, seconds=2.5):
             "source": "amd-smi metric -p -c (read-only) sampled during back-to-back index steps after the timed ones"}
 
 
+DUMP_ROW_EVENTS = 1024    # --dump-outputs: events whose HB / LA rows are written
+DUMP_FC_ANSWERS = 1 << 20   # --dump-outputs: ForklessCause answers written
+DUMP_SEED = 20240607
+
+
+def dump_sample(n, k):
+    """k of range(n), sorted: the same for every run (seeded)."""
+    import numpy as np
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=k, replace=False)).astype(np.int64)
+
+
+def save_npy(dirname, name, a):
+    """a as DIR/<name>.npy: float32 where that holds every value exactly, else float64."""
+    import numpy as np
+    a = np.asarray(a)
+    exact32 = a.size == 0 or int(a.max()) < (1 << 24)
+    np.save(os.path.join(dirname, name + ".npy"), a.astype(np.float32 if exact32 else np.float64))
+
+
+def save_rows(dirname, name, off, buf):
+    """Getter rows (byte offsets[n + 1], bytes) as u32 words: [n, words] when
+    the rows are of one length, else flat with <name>_offsets beside it."""
+    import numpy as np
+    words = np.ascontiguousarray(buf).view(np.uint32)
+    lens = np.diff(off.astype(np.int64)) // 4
+    if len(lens) and (lens == lens[0]).all():
+        save_npy(dirname, name, words.reshape(len(lens), -1))
+    else:
+        save_npy(dirname, name, words)
+        save_npy(dirname, name + "_offsets", off.astype(np.int64) // 4)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -601,6 +652,14 @@ def main():
     ap.add_argument("--order", default="add", choices=["add", "level"],
                     help="event order of the batch: generator (Add) order, or level order as a "
                          "level-synchronous batcher releases the epoch (same DAG, renumbered)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the ForklessCause spot check, power / clock samples, the latency, "
+                         "QuorumIndexer, C1/C2/C4, abft and drop-in legs, the CPU baselines and (N > 1 row segments) "
+                         "the column-shard leg; the --no-* options below switch single legs of it off")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last ones computed as DIR/<name>.npy: the "
+                         "HighestBefore / LowestAfter rows of a fixed sample of events and a fixed sample of the "
+                         "ForklessCause answers")
     ap.add_argument("--cpu-budget", type=float, default=12.0)
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-power", action="store_true",
@@ -814,7 +873,7 @@ def main():
         power = None
         # (not under rocprofv3: its tool library would load into the amd-smi child too)
         profiled = any(k.startswith("ROCPROF") for k in os.environ)
-        if kind == "single" and rank == 0 and world == 1 and not args.no_power and not profiled:
+        if args.full and kind == "single" and rank == 0 and world == 1 and not args.no_power and not profiled:
             power = power_probe(index_step)   # untimed, after the timed steps
 
         # ---- FC: warmup + K timed steps
@@ -860,7 +919,8 @@ def main():
                          "whole_rows": int(early_all[3]), "answered": int(nq_all) * args.steps}
                if early_all[0] else None,
                "whole_row_bytes": 8.0 * B * nq, "st_x": st_x,
-               "mem": ix.device_bytes(), "clk": clk_timed, "power": power}
+               "mem": ix.device_bytes(), "clk": clk_timed, "power": power,
+               "fc_out": d_part if kind == "solo" else d_out}
         if kind == "rowseg":
             out["rsx"] = rsx
             out["proto_split"] = proto_split
@@ -899,7 +959,7 @@ def main():
     # 0 < LA(b)[j] <= HB(a)[j].Seq >= quorum (vecfc/forkless_cause.go:63-82;
     # the bench DAG has no forks)
     spot_n = 0
-    if primary in ("single", "rowseg"):
+    if args.full and primary in ("single", "rowseg"):
         qa_s, qb_s = qa[:4096], qb[:4096]
         got = d_out[:4096].cpu().numpy()
         if primary == "rowseg":
@@ -917,6 +977,31 @@ def main():
         want = (stake >= ix.quorum()).astype(np.uint8)
         assert np.array_equal(got, want), "ForklessCause spot check failed"
         spot_n = int(sum_over_ranks(float(len(got))))
+
+    if args.dump_outputs:
+        # what the last timed steps left for a caller: rows of the index the
+        # last index step built (the getters a caller reads them through) and
+        # the last ForklessCause step's answers; the row getters of the
+        # multi-GPU modes are collective, rank 0 writes
+        ev_s = dump_sample(N, DUMP_ROW_EVENTS).astype(np.uint32)
+        fc_s = dump_sample(args.fc_queries, DUMP_FC_ANSWERS)
+        rows = {}
+        for mode, name in ((0, "highest_before"), (1, "lowest_after")):
+            if primary in ("rowseg", "shard"):
+                rl = [r or b"" for r in P["rsx" if primary == "rowseg" else "sx"].get_rows(mode, ev_s)]
+                off = np.zeros(len(rl) + 1, dtype=np.int64)
+                np.cumsum([len(r) for r in rl], out=off[1:])
+                rows[name] = (off, np.frombuffer(b"".join(rl), dtype=np.uint8))
+            else:
+                rows[name] = ix.rows_np(mode, ev_s)
+        fc_got = P["fc_out"][torch.from_numpy(fc_s).to(dev)].cpu().numpy()
+        if rank == 0:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            save_npy(args.dump_outputs, "row_events", ev_s)
+            for name, (off, buf) in rows.items():
+                save_rows(args.dump_outputs, name, off, buf)
+            save_npy(args.dump_outputs, "fc_query_sample", fc_s)
+            save_npy(args.dump_outputs, "forkless_cause", fc_got)
 
     units = 1 if (shard or rowseg) else world          # shard / rowseg: the ranks share one epoch
     fc_units = 1 if shard else world                   # rowseg / replica: every rank asks its own 2^k queries
@@ -1059,7 +1144,7 @@ def main():
         result["shard"] = {"columns": B, "wire_bytes_per_entry": wire,
                            "exchange_ms": float(np.mean(P["st_x"][-args.steps:])) if P["st_x"] else None,
                            "note": "index step = walk of own columns + LowestAfter all-to-all (timed inside value)"}
-    if rowseg and not args.no_colshard:
+    if args.full and rowseg and not args.no_colshard:
         # BASELINE configs[2] as it names it: the same epoch column-sharded over
         # the same ranks (north_star (5)); the row-segment handle is freed first
         ix.close()
@@ -1092,7 +1177,7 @@ def main():
         cx.close()
         ix = cx
 
-    if not args.no_latency and world == 1 and not solo:
+    if args.full and not args.no_latency and world == 1 and not solo:
         ix.close()   # free the bench epoch's planes first
         result["latency"] = latency_leg(lx, dag, weights, local)
         fl = feed_levels(dag, weights, local)
@@ -1101,13 +1186,13 @@ def main():
         result["latency"]["fed"] = fl
         result["quorum_indexer"] = qi_leg(dag, weights, local, rank == 0 and not args.no_cpu)
 
-    if not args.no_configs and world == 1 and not solo:
+    if args.full and not args.no_configs and world == 1 and not solo:
         ix.close()
         want_cpu = rank == 0 and not args.no_cpu
         result["configs"] = {c: config_leg(lx, c, args.steps, args.warmup, local, want_cpu, min(args.cpu_budget, 4.0))
                              for c in ("c2", "c4", "c1")}
 
-    if not args.no_abft:
+    if args.full and not args.no_abft:
         ab = abft_leg(lx, args.steps, args.warmup, local, args.cpu_budget, rank == 0 and world == 1 and not args.no_cpu)
         barrier()
         ab["ms_per_step"] = max_over_ranks(ab["ms_per_step"])   # replicas: one epoch per rank
@@ -1115,10 +1200,10 @@ def main():
         ab["parallelism"] = "replica%d" % world
         result["abft"] = ab
 
-    if not args.no_dropin and world == 1 and not solo:
+    if args.full and not args.no_dropin and world == 1 and not solo:
         result["dropin_c5"] = dropin_leg(lx, local, rank == 0 and not args.no_cpu)
 
-    if rank == 0 and world == 1 and not args.no_cpu:     # the CPU baseline is an N=1 figure
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:     # the CPU baseline is an N=1 figure
         sample_max = N
         done, t_add, nq, t_q, (nq_mt, t_mt, thr) = cpu_baseline(dag, weights, sample_max, 200_000, args.cpu_budget)
         result["cpu_baseline"] = {

@@ -18,5 +18,5 @@ step pytest_gpu ${PYTEST_T:-900} python -m pytest tests -m gpu -x -q ${PYTEST_AR
 ok_or_fail $rc || exit $rc
 step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"; rc=$?
 ok_or_fail $rc || exit $rc
-step bench ${BENCH_T:-600} python bench.py ${BENCH_ARGS}; rc=$?
+step bench ${BENCH_T:-600} python bench.py --full ${BENCH_ARGS}; rc=$?
 exit $rc

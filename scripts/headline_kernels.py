@@ -19,7 +19,7 @@ def main():
     for f in glob.glob(os.path.join(root, "**", "*kernel_trace.csv"), recursive=True):
         with open(f) as fh:
             rows.extend(csv.DictReader(fh))
-    out = {"source": "rocprofv3 --kernel-trace of `python3 bench.py --no-cpu` (scripts/prof_round.sh)", "kernels": {}}
+    out = {"source": "rocprofv3 --kernel-trace of `python3 bench.py --full --no-cpu` (scripts/prof_round.sh)", "kernels": {}}
     # the C3 walk: one 4-column k_index, or (side-by-side segments)
     # one 8-column k_index_segs launch
     # (the C3 ForklessCause steps run the early-exit kernel since round 5)

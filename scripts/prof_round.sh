@@ -10,7 +10,7 @@ export TMPDIR=/tmp
 O=${OUT:-gpurun_out/prof_round}
 mkdir -p $O
 if [ -z "$PMC_ONLY" ]; then   # PMC_ONLY=1: the counter passes alone
-timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o kt -- python3 bench.py --no-cpu --no-power > $O/kt.log 2>&1 || exit $?
+timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o kt -- python3 bench.py --full --no-cpu --no-power > $O/kt.log 2>&1 || exit $?
 python3 scripts/headline_kernels.py $O/kt > $O/headline_kernels.json || exit $?
 fi
 [ -n "$NO_PMC" ] && { find $O -name "*trace*.csv" -delete; echo done; exit 0; }   # NO_PMC=1: the kernel stats alone

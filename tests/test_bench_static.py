@@ -42,6 +42,57 @@ def test_bench_functions_bind_every_name_they_use():
     assert not bad, bad
 
 
+def test_dump_helpers(tmp_path):
+    """--dump-outputs: the sample is fixed, the files are float32 where that is
+    exact and float64 otherwise, rows of one length come out as a matrix."""
+    import numpy as np
+    import bench
+    s = bench.dump_sample(10_000_000, 1024)
+    assert np.array_equal(s, bench.dump_sample(10_000_000, 1024))
+    assert len(np.unique(s)) == 1024 and (np.diff(s) > 0).all() and 0 <= s[0] and s[-1] < 10_000_000
+    assert np.array_equal(bench.dump_sample(7, 1024), np.arange(7))
+    d = str(tmp_path)
+    bench.save_npy(d, "small", np.array([0, (1 << 24) - 1], dtype=np.uint32))
+    bench.save_npy(d, "large", np.array([0, (1 << 24) + 1], dtype=np.uint32))
+    small, large = np.load(os.path.join(d, "small.npy")), np.load(os.path.join(d, "large.npy"))
+    assert small.dtype == np.float32 and small[1] == (1 << 24) - 1
+    assert large.dtype == np.float64 and large[1] == (1 << 24) + 1
+    words = np.arange(6, dtype=np.uint32)
+    bench.save_rows(d, "even", np.array([0, 12, 24], dtype=np.uint64), words.view(np.uint8))
+    assert np.array_equal(np.load(os.path.join(d, "even.npy")), words.reshape(2, 3))
+    bench.save_rows(d, "ragged", np.array([0, 8, 24], dtype=np.uint64), words.view(np.uint8))
+    assert np.array_equal(np.load(os.path.join(d, "ragged.npy")), words)
+    assert np.array_equal(np.load(os.path.join(d, "ragged_offsets.npy")), [0, 2, 6])
+
+
+def test_plain_run_gates_every_other_leg():
+    """Whatever bench.py measures beside the headline runs under --full only:
+    every call of such a leg in main() sits under a condition that names
+    args.full."""
+    tree = ast.parse(open(os.path.join(ROOT, "bench.py"), encoding="utf-8").read())
+    main = next(n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name == "main")
+    legs = {"latency_leg", "feed_levels", "qi_leg", "config_leg", "abft_leg", "dropin_leg", "cpu_baseline",
+            "power_probe"}
+    seen = set()
+
+    def walk(node, gated):
+        if isinstance(node, ast.If):
+            g = gated or any(isinstance(n, ast.Attribute) and n.attr == "full" for n in ast.walk(node.test))
+            for c in node.body:
+                walk(c, g)
+            for c in node.orelse:
+                walk(c, gated)
+            return
+        if isinstance(node, ast.Call) and isinstance(node.func, ast.Name) and node.func.id in legs:
+            assert gated, (node.func.id, node.lineno)
+            seen.add(node.func.id)
+        for c in ast.iter_child_nodes(node):
+            walk(c, gated)
+
+    walk(main, False)
+    assert seen == legs, legs - seen
+
+
 def test_multi_gpu_line_keys():
     """The committed N = 2 rehearsal line (two ranks over gloo on one GPU,
     scripts/rowseg_rehearsal.sh; the driver's N > 1 runs use RCCL) carries what
