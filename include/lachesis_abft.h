@@ -17,7 +17,8 @@
  * the current epoch; they restart at 0 when an epoch is sealed or reset),
  * validator idx order, caller-owned buffers, 0 = ok / < 0 = error.  The abft
  * handle drives the index handle it was created on (Add, Flush,
- * DropNotFlushed, Reset): do not add events to that index directly.
+ * DropNotFlushed, Reset): do not add events to that index directly (the one
+ * exception is the reload of a persisted epoch before lx_abft_restore).
  * One host thread per handle; callbacks must not call back into the handle.
  */
 #ifndef LACHESIS_ABFT_H
@@ -81,6 +82,67 @@ int lx_abft_set_option(lx_abft *a, const char *name, int64_t value);
 int lx_abft_bootstrap(lx_abft *a, uint32_t epoch, uint32_t n_validators, const uint32_t *weights,
                       const lx_abft_callbacks *cb);
 
+/* IndexedLachesis.Bootstrap over a persisted epoch (abft/indexed_lachesis.go:84-99,
+ * abft/bootstrap.go:34-55, abft/lachesis.go:88-99): resumes an epoch after a
+ * restart from what Orderer.Bootstrap reads back -- epoch, validators, last
+ * decided frame, the roots table (abft/store_roots.go:56-93) and the
+ * confirmed-on table -- instead of replaying the epoch's events.
+ *
+ * Precondition: the caller has reloaded the handle's index for this epoch
+ * (lx_reset with the same validators, lx_load_rows ..., lx_load_finish) with
+ * the same n_events events in the same dense order.  This is the one exception
+ * to "do not add events to that index directly".
+ *
+ * Events: creator_idx / seq / parent_off / parent_idx are the arrays given to
+ * lx_load_rows (self-parent first); ev_frame[e] is the event's frame,
+ * ev_confirmed_on[e] GetEventConfirmedOn (0 = not confirmed).
+ * Roots: frame f (1 .. n_frames) has the slots
+ * root_ev[root_off[f-1] .. root_off[f]) in the order the caller read them
+ * (append order of the cache, or key order of the kvdb table); an event that
+ * is a root of several frames appears in each (AddRoot, store_roots.go:23-27).
+ * The engine keeps that order; new roots are appended behind it.
+ *
+ * The call rebuilds the observed-roots bit rows of every slot above
+ * last_decided_frame (one merged root-ForklessCause launch for all frames) and
+ * then does what bootstrapElection does (event_processing.go:102-146): an
+ * election for last_decided_frame + 1 over every known root, repeated while
+ * frames decide.  As in the reference, Bootstrap runs before the callbacks are
+ * assigned (lachesis.go:92-98): a frame decided during the call advances the
+ * last decided frame with nil-BeginBlock semantics -- no callback, no
+ * confirmation, no seal.  cb takes effect for later batches.
+ *
+ * Errors (message in lx_abft_last_error; all input is checked before any
+ * device work or allocation sized by it): LX_ERR_STATE "already bootstrapped"
+ * on a bootstrapped or restored handle, for a sharded index, an index in the
+ * middle of loading, or validators other than the index's; LX_ERR_ARG for
+ * n_events != lx_num_events(index), a non-monotone root_off, a frame without
+ * roots, more than 16384 roots in a frame, a root index >= n_events or listed
+ * twice in a frame, a slot of frame f whose event does not satisfy
+ * frame(self-parent) < f <= ev_frame[e], a roots table that misses a slot the
+ * event tables imply, last_decided_frame > n_frames, ev_confirmed_on[e] >
+ * last_decided_frame, or event arrays that are not parents-first.  A failed
+ * call leaves the handle not bootstrapped: a second lx_abft_restore or a
+ * plain lx_abft_bootstrap works. */
+int lx_abft_restore(lx_abft *a, uint32_t epoch, uint32_t n_validators, const uint32_t *weights,
+                    uint32_t last_decided_frame, uint32_t n_events, const uint32_t *creator_idx, const uint32_t *seq,
+                    const uint64_t *parent_off, const uint32_t *parent_idx, const uint32_t *ev_frame,
+                    const uint32_t *ev_confirmed_on, uint32_t n_frames, const uint64_t *root_off,
+                    const uint32_t *root_ev, const lx_abft_callbacks *cb);
+
+/* The bulk inverse of lx_abft_restore: the abft state of the current epoch as
+ * a caller persists it (or copies it, abft/restart_test.go:159-175).
+ * lx_abft_state_sizes gives the counts; lx_abft_state_fetch fills ev_frame and
+ * ev_confirmed_on (n_events entries), root_off (n_frames + 1 entries) and
+ * root_ev (n_slots entries, frames 1 .. n_frames in slot order).  Any pointer
+ * may be NULL.  n_frames = the highest frame holding a root. */
+typedef struct lx_abft_state {
+    uint32_t epoch, last_decided_frame, n_events, n_frames;
+    uint64_t n_slots;
+} lx_abft_state;
+int lx_abft_state_sizes(lx_abft *a, lx_abft_state *out);
+int lx_abft_state_fetch(lx_abft *a, uint32_t *ev_frame, uint32_t *ev_confirmed_on, uint64_t *root_off,
+                        uint32_t *root_ev);
+
 /* Orderer.Reset (bootstrap.go:54-65): switch to a new empty epoch. */
 int lx_abft_reset(lx_abft *a, uint32_t epoch, uint32_t n_validators, const uint32_t *weights);
 
@@ -125,7 +187,10 @@ int lx_abft_event_frame(const lx_abft *a, uint32_t ev, uint32_t *frame);
 /* GetEventConfirmedOn (abft/store_event_confirmed.go:20-30): 0 = not confirmed. */
 int lx_abft_event_confirmed_on(const lx_abft *a, uint32_t ev, uint32_t *frame);
 
-/* Wall time of the last lx_abft_process_batch by phase (ms) and its GPU work. */
+/* Wall time of the last lx_abft_process_batch by phase (ms) and its GPU work.
+ * After lx_abft_restore: ms_frames = input checks, tables and the rebuild of
+ * the bit rows (fc_launches, fc_pairs), ms_election = the elections
+ * (vote_launches); ms_index is 0 (the index reload is the caller's). */
 typedef struct lx_abft_stats {
     float ms_index;      /* Add of the batch (lx_add_batch) */
     float ms_frames;     /* frames + roots (root ForklessCause tiles) */

@@ -627,6 +627,114 @@ int eval_frame(lx_abft *a, const IndexView &iv, uint32_t f, const std::vector<ui
     return collect_fc_times(a);
 }
 
+// One step of a merged root-FC launch: cand[0, n_cand) against the first
+// n_roots slots of frame `frame`; bit rows (words each) at arena word row0, q
+// answers at q_dev + qoff.  n_cand and words are not 0.
+struct FcStep {
+    uint32_t frame;
+    const uint32_t *cand;
+    uint32_t n_cand, n_roots, words;
+    uint64_t row0, qoff;
+};
+
+// Many steps in one k_root_fc and one k_root_quorum launch (the MULTI forms;
+// the arena already holds room for every row): enqueued, nothing waits.
+int launch_fc_steps(lx_abft *a, const IndexView &iv, const std::vector<FcStep> &st, uint8_t *q_dev, PassTimer *pt) {
+    if (st.empty()) return 0;
+    hipStream_t s = iv.stream;
+    uint64_t ncand = 0, tiles = 0;
+    for (const FcStep &x : st) {
+        ARC(sync_frame(a, frame_at(a, x.frame), s));
+        ncand += x.n_cand;
+        tiles += (uint64_t)((x.n_roots + 63) / 64) * ((x.n_cand + 63) / 64);
+    }
+    const uint32_t ncols = (iv.V + 31) / 32 * 32;
+    const uint32_t max_s = ncols / 128 ? ncols / 128 : 1;   // >= 4 LDS chunks of 32 columns per split
+    const uint32_t splits = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((1024 + tiles - 1) / tiles, 1), max_s);
+    const uint32_t col_split = ((ncols + splits - 1) / splits + 31) / 32 * 32;
+    const uint32_t n_split = (ncols + col_split - 1) / col_split;
+    uint64_t npsum = 0;
+    for (const FcStep &x : st) npsum += (uint64_t)n_split * x.n_cand * x.words * 32;
+    ARC(reserve(a, a->d_cand, ncand, 0, s));
+    ARC(reserve(a, a->d_psum, npsum, 0, s));
+    ARC(reserve(a, a->d_fcargs, st.size(), 0, s));
+    ARC(reserve(a, a->d_qargs, st.size(), 0, s));
+    ARC(refresh_cheaters(a, iv));
+    std::vector<RootFcArgs> fa(st.size());
+    std::vector<QuorumArgs> qa(st.size());
+    uint64_t coff = 0, poff = 0, pairs = 0;
+    uint32_t blocks = 0, qblocks = 0;
+    for (size_t j = 0; j < st.size(); j++) {
+        const FcStep &x = st[j];
+        Frame &fr = a->frames[x.frame];
+        a->up.add(a->d_cand.p + coff, x.cand, x.n_cand * 4ull);
+        RootFcArgs &r = fa[j];
+        r.hb = iv.hb;
+        r.la = iv.la;
+        r.stride = iv.stride;
+        r.cand = a->d_cand.p + coff;
+        r.n_cand = x.n_cand;
+        r.roots = fr.d_ev.p;
+        r.n_roots = x.n_roots;
+        r.roots_fallback = x.cand[0];
+        r.ncols = ncols;
+        r.wpad = iv.wpad;
+        r.quorum = a->quorum;
+        r.n_k = a->n_k;
+        r.kcol = a->d_kcol.p;
+        r.kflag = a->d_kflag.p;
+        r.kw = a->d_kw.p;
+        r.ev_branch = iv.ev_branch;
+        r.psum = a->d_psum.p + poff;
+        r.words = x.words;
+        r.col_split = col_split;
+        r.n_split = n_split;
+        r.block0 = blocks;
+        blocks += lx::root_fc_blocks(r);
+        QuorumArgs &q = qa[j];
+        q.psum = r.psum;
+        q.n_split = n_split;
+        q.bits = a->arena.p + x.row0;
+        q.words = x.words;
+        q.n_roots = x.n_roots;
+        q.n_cand = x.n_cand;
+        q.cand = r.cand;
+        q.root_ev = fr.d_ev.p;
+        q.creator = fr.d_creator.p;
+        q.dup = fr.d_dup.p;
+        q.wcreator = iv.wpad;
+        q.quorum = a->quorum;
+        q.q = q_dev + x.qoff;
+        q.block0 = qblocks;
+        qblocks += (x.n_cand + 3) / 4;
+        coff += x.n_cand;
+        poff += (uint64_t)n_split * x.n_cand * x.words * 32;
+        pairs += (uint64_t)x.n_cand * x.n_roots;
+    }
+    a->stats.fc_pairs += pairs;
+    a->stats.fc_pair_cols += pairs * iv.V;
+    a->up.add(a->d_fcargs.p, fa.data(), fa.size() * sizeof(RootFcArgs));
+    a->up.add(a->d_qargs.p, qa.data(), qa.size() * sizeof(QuorumArgs));
+    if (pt) pt->mark("args");
+    ARC(flush_uploads(a, s));
+    if (pt) pt->mark("upload");
+    const bool forks = iv.B > iv.V, seq16 = a->fc16 && iv.max_seq <= 0xFFFFu;
+    const uint32_t k = a->fc_ev_used;
+    while (a->fc_ev.size() < 2ull * (k + 1)) {
+        hipEvent_t e;
+        AHIP(a, hipEventCreate(&e));
+        a->fc_ev.push_back(e);
+    }
+    AHIP(a, hipEventRecord(a->fc_ev[2 * k], s));
+    AHIP(a, lx::launch_root_fc_multi(a->d_fcargs.p, (uint32_t)st.size(), blocks, forks, seq16, s));
+    AHIP(a, hipEventRecord(a->fc_ev[2 * k + 1], s));
+    a->fc_ev_used = k + 1;
+    AHIP(a, lx::launch_root_quorum_multi(a->d_qargs.p, (uint32_t)st.size(), qblocks, s));
+    a->stats.fc_launches++;
+    a->stats.fc_lane_ops += pairs * fc_ops_per_pair(a, iv, forks, seq16, ncols);
+    return 0;
+}
+
 // Frames of a batch in which every event claims its frame (Process,
 // event_processing.go:163-189 with the claimed frame as the loop bound).
 // Taking the claims of in-batch self-parents as given, every question is
@@ -762,101 +870,11 @@ int compute_frames_claimed(lx_abft *a, uint64_t base, uint32_t n, const uint32_t
     pt.mark("slots");
     // every step in one k_root_fc and one k_root_quorum launch
     ARC(reserve(a, a->arena, a->arena_used + 1, arena0, s));
-    uint64_t ncand = 0, tiles = 0;
-    std::vector<uint32_t> act;
+    std::vector<FcStep> act;
     for (uint32_t k = 0; k < nf; k++)
-        if (launched[k]) {
-            ARC(sync_frame(a, frame_at(a, fmin + k), s));
-            act.push_back(k);
-            ncand += cand[k].size();
-            tiles += (uint64_t)((nroots[k] + 63) / 64) * ((cand[k].size() + 63) / 64);
-        }
-    if (!act.empty()) {
-        const uint32_t ncols = (iv.V + 31) / 32 * 32;
-        const uint32_t max_s = ncols / 128 ? ncols / 128 : 1;   // >= 4 LDS chunks of 32 columns per split
-        const uint32_t splits = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((1024 + tiles - 1) / tiles, 1), max_s);
-        const uint32_t col_split = ((ncols + splits - 1) / splits + 31) / 32 * 32;
-        const uint32_t n_split = (ncols + col_split - 1) / col_split;
-        uint64_t npsum = 0;
-        for (uint32_t k : act) npsum += (uint64_t)n_split * cand[k].size() * words[k] * 32;
-        ARC(reserve(a, a->d_cand, ncand, 0, s));
-        ARC(reserve(a, a->d_psum, npsum, 0, s));
-        ARC(reserve(a, a->d_fcargs, act.size(), 0, s));
-        ARC(reserve(a, a->d_qargs, act.size(), 0, s));
-        ARC(refresh_cheaters(a, iv));
-        std::vector<RootFcArgs> fa(act.size());
-        std::vector<QuorumArgs> qa(act.size());
-        uint64_t coff = 0, poff = 0, pairs = 0;
-        uint32_t blocks = 0, qblocks = 0;
-        for (size_t j = 0; j < act.size(); j++) {
-            const uint32_t k = act[j], n_k = (uint32_t)cand[k].size();
-            Frame &fr = a->frames[fmin + k];
-            a->up.add(a->d_cand.p + coff, cand[k].data(), n_k * 4ull);
-            RootFcArgs &r = fa[j];
-            r.hb = iv.hb;
-            r.la = iv.la;
-            r.stride = iv.stride;
-            r.cand = a->d_cand.p + coff;
-            r.n_cand = n_k;
-            r.roots = fr.d_ev.p;
-            r.n_roots = nroots[k];
-            r.roots_fallback = cand[k][0];
-            r.ncols = ncols;
-            r.wpad = iv.wpad;
-            r.quorum = a->quorum;
-            r.n_k = a->n_k;
-            r.kcol = a->d_kcol.p;
-            r.kflag = a->d_kflag.p;
-            r.kw = a->d_kw.p;
-            r.ev_branch = iv.ev_branch;
-            r.psum = a->d_psum.p + poff;
-            r.words = words[k];
-            r.col_split = col_split;
-            r.n_split = n_split;
-            r.block0 = blocks;
-            blocks += lx::root_fc_blocks(r);
-            QuorumArgs &q = qa[j];
-            q.psum = r.psum;
-            q.n_split = n_split;
-            q.bits = a->arena.p + row0[k];
-            q.words = words[k];
-            q.n_roots = nroots[k];
-            q.n_cand = n_k;
-            q.cand = r.cand;
-            q.root_ev = fr.d_ev.p;
-            q.creator = fr.d_creator.p;
-            q.dup = fr.d_dup.p;
-            q.wcreator = iv.wpad;
-            q.quorum = a->quorum;
-            q.q = q_dev + qoff[k];
-            q.block0 = qblocks;
-            qblocks += (n_k + 3) / 4;
-            coff += n_k;
-            poff += (uint64_t)n_split * n_k * words[k] * 32;
-            pairs += (uint64_t)n_k * nroots[k];
-        }
-        a->stats.fc_pairs += pairs;
-        a->stats.fc_pair_cols += pairs * iv.V;
-        a->up.add(a->d_fcargs.p, fa.data(), fa.size() * sizeof(RootFcArgs));
-        a->up.add(a->d_qargs.p, qa.data(), qa.size() * sizeof(QuorumArgs));
-        pt.mark("args");
-        ARC(flush_uploads(a, s));
-        pt.mark("upload");
-        const bool forks = iv.B > iv.V, seq16 = a->fc16 && iv.max_seq <= 0xFFFFu;
-        const uint32_t k = a->fc_ev_used;
-        while (a->fc_ev.size() < 2ull * (k + 1)) {
-            hipEvent_t e;
-            AHIP(a, hipEventCreate(&e));
-            a->fc_ev.push_back(e);
-        }
-        AHIP(a, hipEventRecord(a->fc_ev[2 * k], s));
-        AHIP(a, lx::launch_root_fc_multi(a->d_fcargs.p, (uint32_t)act.size(), blocks, forks, seq16, s));
-        AHIP(a, hipEventRecord(a->fc_ev[2 * k + 1], s));
-        a->fc_ev_used = k + 1;
-        AHIP(a, lx::launch_root_quorum_multi(a->d_qargs.p, (uint32_t)act.size(), qblocks, s));
-        a->stats.fc_launches++;
-        a->stats.fc_lane_ops += pairs * fc_ops_per_pair(a, iv, forks, seq16, ncols);
-    }
+        if (launched[k])
+            act.push_back(FcStep{fmin + k, cand[k].data(), (uint32_t)cand[k].size(), nroots[k], words[k], row0[k], qoff[k]});
+    ARC(launch_fc_steps(a, iv, act, q_dev, &pt));
     pt.mark("launch");
     AHIP(a, hipStreamSynchronize(s));
     pt.mark("wait");
@@ -1388,6 +1406,156 @@ int run_elections(lx_abft *a, uint64_t *sealed_at, std::vector<uint32_t> *new_w)
     }
 }
 
+// ---------------------------------------------------------------------------- restart
+
+// What lx_abft_restore is given (include/lachesis_abft.h).
+struct RestoreIn {
+    uint32_t epoch, nv;
+    const uint32_t *w;
+    uint32_t last_decided, n;
+    const uint32_t *creator, *seq;
+    const uint64_t *poff;
+    const uint32_t *par, *ev_frame, *ev_conf;
+    uint32_t nf;
+    const uint64_t *root_off;
+    const uint32_t *root_ev;
+};
+
+// Every check of the input, on the host: nothing is allocated by a size the
+// caller claims before that size is tied to the index's own event count (the
+// two tables below have n_events entries, checked first; the roots are read in
+// place, and a frame's slot list ends at its first repeated event at the
+// latest).  *sp_out = self-parent per event (inter/dag/event.go:87-92).
+int check_restore(lx_abft *a, const IndexView &iv, const RestoreIn &in, std::vector<uint32_t> *sp_out) {
+    if (!in.nv || !in.w) return a->fail(LX_ERR_ARG, "genesis validators shouldn't be empty");
+    if (iv.shard_count > 1) return a->fail(LX_ERR_STATE, "abft needs an unsharded index");
+    if (iv.loading) return a->fail(LX_ERR_STATE, "index is loading (lx_load_finish first)");
+    if (in.nv != iv.V || !std::equal(in.w, in.w + in.nv, iv.weights->begin()))
+        return a->fail(LX_ERR_STATE, "validators differ from the ones the index was reloaded with");
+    if (in.n != iv.n_events)
+        return a->fail(LX_ERR_ARG, "n_events %u, but the index holds %llu events", in.n, (unsigned long long)iv.n_events);
+    if (in.n && (!in.creator || !in.seq || !in.poff || !in.ev_frame || !in.ev_conf))
+        return a->fail(LX_ERR_ARG, "null event table");
+    if (in.nf && !in.root_off) return a->fail(LX_ERR_ARG, "null root_off");
+    if (in.last_decided > in.nf)
+        return a->fail(LX_ERR_ARG, "last decided frame %u above the %u frames of the roots table", in.last_decided, in.nf);
+    std::vector<uint32_t> &sp = *sp_out;
+    sp.assign(in.n, NONE);
+    uint64_t want_slots = 0;
+    for (uint32_t e = 0; e < in.n; e++) {
+        const uint64_t p0 = in.poff[e], p1 = in.poff[e + 1];
+        if (p1 < p0 || (p1 > p0 && !in.par)) return a->fail(LX_ERR_ARG, "event %u: bad parent_off", e);
+        if (in.creator[e] >= in.nv) return a->fail(LX_ERR_ARG, "event %u: creator idx %u", e, in.creator[e]);
+        for (uint64_t x = p0; x < p1; x++)
+            if (in.par[x] >= e) return a->fail(LX_ERR_ARG, "event %u: parent %u is not before it", e, in.par[x]);
+        if (in.seq[e] > 1 && p1 > p0) sp[e] = in.par[p0];
+        const uint32_t spf = sp[e] == NONE ? 0 : in.ev_frame[sp[e]], f = in.ev_frame[e];
+        if (f == 0 || f < spf || f > in.nf)
+            return a->fail(LX_ERR_ARG, "event %u: frame %u (self-parent's frame %u, %u frames of roots)", e, f, spf, in.nf);
+        want_slots += f - spf;   // a root of every frame it passes (store_roots.go:23-27)
+        if (in.ev_conf[e] > in.last_decided)
+            return a->fail(LX_ERR_ARG, "event %u confirmed on frame %u above the last decided frame %u", e, in.ev_conf[e],
+                           in.last_decided);
+    }
+    if (in.nf && in.root_off[0] != 0) return a->fail(LX_ERR_ARG, "root_off must start at 0");
+    std::vector<uint32_t> seen(in.n, 0);   // last frame listing the event
+    for (uint32_t f = 1; f <= in.nf; f++) {
+        const uint64_t lo = in.root_off[f - 1], hi = in.root_off[f];
+        if (hi < lo) return a->fail(LX_ERR_ARG, "root_off is not monotone at frame %u", f);
+        if (hi == lo) return a->fail(LX_ERR_ARG, "frame %u has no roots", f);
+        if (!in.root_ev) return a->fail(LX_ERR_ARG, "null root_ev");
+        if (hi - lo > kMaxFrameRoots) return a->fail(LX_ERR_ARG, "frame %u: more than %u roots", f, kMaxFrameRoots);
+        for (uint64_t k = lo; k < hi; k++) {
+            const uint32_t e = in.root_ev[k];
+            if (e >= in.n) return a->fail(LX_ERR_ARG, "frame %u: root %u is not an event of the epoch", f, e);
+            if (seen[e] == f) return a->fail(LX_ERR_ARG, "frame %u lists root %u twice", f, e);
+            seen[e] = f;
+            const uint32_t spf = sp[e] == NONE ? 0 : in.ev_frame[sp[e]];
+            if (!(spf < f && f <= in.ev_frame[e]))
+                return a->fail(LX_ERR_ARG, "frame %u: event %u (frame %u, self-parent's %u) is no root of it", f, e,
+                               in.ev_frame[e], spf);
+        }
+    }
+    const uint64_t slots = in.nf ? in.root_off[in.nf] : 0;
+    if (slots != want_slots)
+        return a->fail(LX_ERR_ARG, "the roots table holds %llu slots, the event frames imply %llu",
+                       (unsigned long long)slots, (unsigned long long)want_slots);
+    return 0;
+}
+
+// The tables of the persisted epoch, the observed-roots bit rows of the slots
+// above the last decided frame, and bootstrapElection (event_processing.go:
+// 102-146).  The bit row of a slot of frame f is not persisted (the reference
+// asks ForklessCause again, election.go:110-124): it is rebuilt as
+// FC(slot, r) over ALL slots r of frame f - 1, one step per frame in one
+// merged launch.  While the epoch ran, the row was taken when the event was
+// processed and covered only the slots of f - 1 known by then (bm_len); the
+// slots added later are later events, not ancestors of this one, so their
+// ForklessCause is false and the full-length row reads the same.
+int restore_epoch(lx_abft *a, const IndexView &iv, const RestoreIn &in, std::vector<uint32_t> &sp) {
+    hipStream_t s = iv.stream;
+    const double t0 = now_ms();
+    clear_epoch(a);
+    a->epoch = in.epoch;
+    a->V = in.nv;
+    a->weights.assign(in.w, in.w + in.nv);
+    a->quorum = iv.quorum;
+    a->last_decided = in.last_decided;
+    a->ev_sp.swap(sp);
+    if (in.n) {
+        a->ev_frame.assign(in.ev_frame, in.ev_frame + in.n);
+        a->ev_confirmed.assign(in.ev_conf, in.ev_conf + in.n);
+        a->par_off.resize((size_t)in.n + 1);
+        for (uint32_t e = 0; e <= in.n; e++) a->par_off[e] = in.poff[e] - in.poff[0];
+        if (in.poff[in.n] > in.poff[0]) a->par.assign(in.par + in.poff[0], in.par + in.poff[in.n]);
+    }
+    a->frames.resize((size_t)in.nf + 1);
+    std::vector<FcStep> steps;
+    uint64_t ncand = 0;
+    for (uint32_t f = 1; f <= in.nf; f++) {
+        const uint64_t lo = in.root_off[f - 1], hi = in.root_off[f];
+        const uint32_t cnt = (uint32_t)(hi - lo);
+        const bool rebuild = f > in.last_decided && f >= 2;   // frame 1 observes nothing
+        const uint32_t R = rebuild ? (uint32_t)a->frames[f - 1].ev.size() : 0, words = (R + 31) / 32;
+        Frame &fr = a->frames[f];
+        fr.ev.reserve(cnt);
+        fr.creator.reserve(cnt);
+        fr.dup.reserve(cnt);
+        fr.bm_off.reserve(cnt);
+        fr.bm_len.reserve(cnt);
+        for (uint32_t k = 0; k < cnt; k++) {
+            const uint32_t e = in.root_ev[lo + k];
+            add_slot(a, f, e, in.creator[e], rebuild ? a->arena_used + (uint64_t)k * words : 0, R);
+        }
+        if (rebuild) {
+            steps.push_back(FcStep{f - 1, a->frames[f].ev.data(), cnt, R, words, a->arena_used, ncand});
+            a->arena_used += (uint64_t)cnt * words;
+            ncand += cnt;
+        }
+    }
+    ARC(reserve(a, a->arena, a->arena_used + 1, 0, s));
+    uint8_t *q_dev = nullptr;   // the quorum answers of the steps are not used
+    ARC(q_buffer(a, std::max<uint64_t>(ncand, 1), s, &q_dev));
+    ARC(launch_fc_steps(a, iv, steps, q_dev, nullptr));
+    AHIP(a, hipStreamSynchronize(s));
+    ARC(collect_fc_times(a));
+    a->stats.frame_steps += (uint32_t)steps.size();
+    const double t1 = now_ms();
+    a->stats.ms_frames += (float)(t1 - t0);
+    // Orderer.Bootstrap runs before the callbacks are assigned (lachesis.go:
+    // 92-98): frames decided here only move the last decided frame
+    // (apply_block without BeginBlock and without the block log)
+    const uint32_t block_log = a->block_log;
+    a->cb = lx_abft_callbacks{};
+    a->block_log = 0;
+    uint64_t sealed_at;
+    std::vector<uint32_t> new_w;
+    const int rc = run_elections(a, &sealed_at, &new_w);
+    a->block_log = block_log;
+    a->stats.ms_election += (float)(now_ms() - t1);
+    return rc;
+}
+
 struct Snapshot {
     std::vector<size_t> sizes;
     uint64_t arena_used;
@@ -1553,6 +1721,64 @@ int lx_abft_bootstrap(lx_abft *a, uint32_t epoch, uint32_t nv, const uint32_t *w
     a->cb = cb ? *cb : lx_abft_callbacks{};
     ARC(start_epoch(a, epoch, nv, w));
     a->booted = true;
+    return 0;
+}
+
+int lx_abft_restore(lx_abft *a, uint32_t epoch, uint32_t nv, const uint32_t *w, uint32_t last_decided, uint32_t n,
+                    const uint32_t *creator, const uint32_t *seq, const uint64_t *poff, const uint32_t *par,
+                    const uint32_t *ev_frame, const uint32_t *ev_conf, uint32_t nf, const uint64_t *root_off,
+                    const uint32_t *root_ev, const lx_abft_callbacks *cb) {
+    if (!a) return LX_ERR_ARG;
+    if (a->booted) return a->fail(LX_ERR_STATE, "already bootstrapped");
+    IndexView iv;
+    int rc = lx_index_view(a->ix, &iv);   // refuses an index without an epoch
+    if (rc) return a->ixfail(rc);
+    const RestoreIn in{epoch, nv, w, last_decided, n, creator, seq, poff, par, ev_frame, ev_conf, nf, root_off, root_ev};
+    std::vector<uint32_t> sp;
+    ARC(check_restore(a, iv, in, &sp));
+    a->stats = lx_abft_stats{};
+    a->blog.clear();
+    rc = restore_epoch(a, iv, in, sp);
+    if (rc) {
+        // not bootstrapped: another restore or a plain bootstrap starts over
+        clear_epoch(a);
+        a->cb = lx_abft_callbacks{};
+        return rc;
+    }
+    a->cb = cb ? *cb : lx_abft_callbacks{};
+    a->booted = true;
+    return 0;
+}
+
+int lx_abft_state_sizes(lx_abft *a, lx_abft_state *out) {
+    if (!a || !out) return LX_ERR_ARG;
+    if (!a->booted) return a->fail(LX_ERR_STATE, "not bootstrapped");
+    uint32_t nf = 0;
+    uint64_t slots = 0;
+    for (uint32_t f = 1; f < a->frames.size(); f++)
+        if (!a->frames[f].ev.empty()) nf = f;
+    for (uint32_t f = 1; f <= nf; f++) slots += a->frames[f].ev.size();
+    out->epoch = a->epoch;
+    out->last_decided_frame = a->last_decided;
+    out->n_events = (uint32_t)a->ev_frame.size();
+    out->n_frames = nf;
+    out->n_slots = slots;
+    return 0;
+}
+
+int lx_abft_state_fetch(lx_abft *a, uint32_t *ev_frame, uint32_t *ev_conf, uint64_t *root_off, uint32_t *root_ev) {
+    lx_abft_state st;
+    ARC(lx_abft_state_sizes(a, &st));
+    if (ev_frame) std::copy(a->ev_frame.begin(), a->ev_frame.end(), ev_frame);
+    if (ev_conf) std::copy(a->ev_confirmed.begin(), a->ev_confirmed.end(), ev_conf);
+    uint64_t off = 0;
+    if (root_off) root_off[0] = 0;
+    for (uint32_t f = 1; f <= st.n_frames; f++) {
+        const auto &ev = a->frames[f].ev;
+        if (root_ev) std::copy(ev.begin(), ev.end(), root_ev + off);
+        off += ev.size();
+        if (root_off) root_off[f] = off;
+    }
     return 0;
 }
 

@@ -368,6 +368,7 @@ hipError_t launch_root_fc_multi(const RootFcArgs *am, uint32_t n_steps, uint32_t
 // distinct creators of the roots it forkless-causes (dup[r] = previous root of
 // the same creator in the frame list), its own root slot excluded.
 constexpr uint32_t kRowWords = 512;   // bit row kept in LDS: up to 16384 roots per frame
+static_assert(kRowWords * 32 == kMaxFrameRoots, "lx_abft_restore checks a frame's slot count against this");
 template <bool MULTI>
 __global__ __launch_bounds__(256) void k_root_quorum(QuorumArgs a1, const QuorumArgs *am, uint32_t n_steps) {
     __shared__ uint32_t sRow[4][kRowWords];

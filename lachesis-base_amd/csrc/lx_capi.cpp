@@ -3585,5 +3585,6 @@ int lx_index_view(lx_index *h, IndexView *o) {
     o->weights = &h->weights;
     o->by_creator = &h->by_creator;
     o->shard_count = h->shard_count;
+    o->loading = h->loading;
     return 0;
 }

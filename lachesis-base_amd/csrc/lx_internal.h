@@ -557,6 +557,7 @@ struct RootFcArgs {
     uint32_t block0;             // merged launch: this step's first workgroup
 };
 
+constexpr uint32_t kMaxFrameRoots = 16384;   // k_root_quorum keeps a candidate's bit row in LDS
 struct QuorumArgs {
     const uint32_t *psum;        // partial stake sums of k_root_fc
     uint32_t n_split;
@@ -807,5 +808,6 @@ struct IndexView {
     const std::vector<uint32_t> *weights;
     const std::vector<std::vector<uint32_t>> *by_creator;
     uint32_t shard_count;
+    bool loading;                // between lx_load_rows and lx_load_finish
 };
 int lx_index_view(lx_index *h, IndexView *out);

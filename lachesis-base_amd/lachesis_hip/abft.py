@@ -13,6 +13,10 @@ abft/common_test.go drives FakeLachesis:
   (abft/indexed_lachesis.go:53-82); ``process_batch(events)`` processes many
   events in one call with the same results
 * ``reset(epoch, validators)``             -- Orderer.Reset (abft/bootstrap.go:54-65)
+* ``state()`` / ``restore(state, index_db, get_event, begin_block)`` -- the
+  abft state a caller persists, and Bootstrap over it after a restart
+  (abft/bootstrap.go:34-55 over a non-empty Store; lx_abft_state_fetch,
+  lx_abft_restore) instead of replaying the epoch
 * ``store``                                -- the bits of abft.Store the tests read
   (GetEpoch, GetValidators, GetLastDecidedFrame, GetFrameRoots,
   GetEventConfirmedOn)
@@ -80,6 +84,46 @@ class AbftStats(ctypes.Structure):
                 ("vote_launches", ctypes.c_uint32), ("blocks", ctypes.c_uint32), ("fc_pairs", ctypes.c_uint64),
                 ("fc_pair_cols", ctypes.c_uint64), ("ms_root_fc_gpu", ctypes.c_float),
                 ("fc_lane_ops", ctypes.c_uint64), ("elections_ahead", ctypes.c_uint32)]
+
+
+class AbftState(ctypes.Structure):
+    _fields_ = [("epoch", ctypes.c_uint32), ("last_decided_frame", ctypes.c_uint32), ("n_events", ctypes.c_uint32),
+                ("n_frames", ctypes.c_uint32), ("n_slots", ctypes.c_uint64)]
+
+
+def _fetch_state(L, h, chk):
+    """lx_abft_state_sizes + lx_abft_state_fetch: the abft state of the
+    current epoch on dense event indices."""
+    st = AbftState()
+    chk(L.lx_abft_state_sizes(h, ctypes.byref(st)))
+    ev_frame = np.zeros(max(st.n_events, 1), dtype=np.uint32)
+    ev_conf = np.zeros(max(st.n_events, 1), dtype=np.uint32)
+    root_off = np.zeros(st.n_frames + 1, dtype=np.uint64)
+    root_ev = np.zeros(max(st.n_slots, 1), dtype=np.uint32)
+    chk(L.lx_abft_state_fetch(h, _p(ev_frame, u32p), _p(ev_conf, u32p), _p(root_off, u64p), _p(root_ev, u32p)))
+    return dict(epoch=st.epoch, last_decided_frame=st.last_decided_frame, ev_frame=ev_frame[:st.n_events],
+                ev_confirmed_on=ev_conf[:st.n_events], root_off=root_off, root_ev=root_ev[:st.n_slots])
+
+
+def restore_arrays(L, h, state, weights, creator, seq, poff, par, cb):
+    """lx_abft_restore on a handle whose index was reloaded: ``state`` as
+    ``state()`` returns it, the events as given to lx_load_rows.  Returns the
+    library's return code (the message stays in lx_abft_last_error)."""
+    w = np.ascontiguousarray(weights, dtype=np.uint32)
+    creator = np.ascontiguousarray(creator, dtype=np.uint32)
+    seq = np.ascontiguousarray(seq, dtype=np.uint32)
+    poff = np.ascontiguousarray(poff, dtype=np.uint64)
+    par = np.ascontiguousarray(par if len(par) else [0], dtype=np.uint32)
+    ev_frame = np.ascontiguousarray(state["ev_frame"], dtype=np.uint32)
+    ev_conf = np.ascontiguousarray(state["ev_confirmed_on"], dtype=np.uint32)
+    root_off = np.ascontiguousarray(state["root_off"], dtype=np.uint64)
+    root_ev = np.ascontiguousarray(state["root_ev"] if len(state["root_ev"]) else [0], dtype=np.uint32)
+    if len(creator) != len(ev_frame) or len(ev_conf) != len(ev_frame) or len(poff) != len(creator) + 1:
+        raise ValueError("abft state and event arrays differ in length")
+    return L.lx_abft_restore(h, int(state["epoch"]), len(w), _p(w, u32p), int(state["last_decided_frame"]),
+                             len(ev_frame), _p(creator, u32p), _p(seq, u32p), _p(poff, u64p), _p(par, u32p),
+                             _p(ev_frame, u32p), _p(ev_conf, u32p), len(root_off) - 1, _p(root_off, u64p),
+                             _p(root_ev, u32p), None if cb is None else ctypes.byref(cb))
 
 
 class _StoreView:
@@ -171,12 +215,47 @@ class IndexedLachesis:
 
     def bootstrap(self, begin_block=None):
         """Bootstrap (abft/indexed_lachesis.go:84-99, abft/lachesis.go:88-100)."""
+        cb = self._callbacks(begin_block)
+        w = np.ascontiguousarray(self.validators.weights, dtype=np.uint32)
+        self._chk(self.L.lx_abft_bootstrap(self.h, self.genesis_epoch, len(w), _p(w, u32p), ctypes.byref(cb)))
+
+    def _callbacks(self, begin_block):
         self._begin_block = begin_block
         cb = Callbacks(None, BEGIN_BLOCK(self._on_begin) if begin_block is not None else BEGIN_BLOCK(),
                        APPLY_EVENT(self._on_apply), END_BLOCK(self._on_end))
         self._keep = cb
-        w = np.ascontiguousarray(self.validators.weights, dtype=np.uint32)
-        self._chk(self.L.lx_abft_bootstrap(self.h, self.genesis_epoch, len(w), _p(w, u32p), ctypes.byref(cb)))
+        return cb
+
+    def state(self):
+        """The abft state of the current epoch as a caller persists it
+        (lx_abft_state_fetch): ``epoch``, ``last_decided_frame``, ``ids`` (event
+        ids in dense order), ``ev_frame`` / ``ev_confirmed_on`` per event,
+        ``root_off`` / ``root_ev`` (dense indices; frame f = slots
+        root_off[f-1] .. root_off[f], in slot order)."""
+        st = _fetch_state(self.L, self.h, self._chk)
+        st["ids"] = [e.id for e in self.evs]
+        return st
+
+    def restore(self, state, index_db, get_event, begin_block=None):
+        """Bootstrap over a persisted epoch (abft/indexed_lachesis.go:84-99
+        over a non-empty Store, abft/restart_test.go:156-188) on a handle that
+        was not bootstrapped, built with the epoch's validators: reloads the
+        index from ``index_db`` (tables "S" / "s" / "b" keyed by event id and
+        "B", as :meth:`VecfcIndex.flush` writes them) in the dense order of
+        ``state["ids"]``, then lx_abft_restore.  Frames decided during the
+        call fire no callbacks (lachesis.go:92-98)."""
+        from .vecfc import load_epoch_tables
+        ids = list(state["ids"])
+        self.ix.reset(self.validators.weights)
+        load_epoch_tables(self.ix, self.validators, index_db, get_event, order=ids)
+        evs = [get_event(i) for i in ids]
+        self.pos, self.evs = {}, []
+        creator, seq, off, flat = self._dense(evs)
+        cb = self._callbacks(begin_block)
+        rc = restore_arrays(self.L, self.h, state, self.validators.weights, creator, seq, off, flat, cb)
+        self._chk(rc)
+        self.evs = evs
+        self.pos = {e.id: k for k, e in enumerate(evs)}
 
     def reset(self, epoch, validators):
         """Orderer.Reset (abft/bootstrap.go:54-65)."""
@@ -293,7 +372,10 @@ class DenseLachesis:
     block itself (option block_log, with the confirmed events when
     apply_events) and the blocks are read after each batch; never seals."""
 
-    def __init__(self, weights, epoch=1, device=0, event_capacity=0, apply_events=True, seal=None, block_log=False):
+    def __init__(self, weights, epoch=1, device=0, event_capacity=0, apply_events=True, seal=None, block_log=False,
+                 bootstrap=True):
+        """``bootstrap=False``: the handle is created but not bootstrapped;
+        :meth:`restore` resumes a persisted epoch on it."""
         self.ix = Index(device=device, event_capacity=event_capacity)
         self.L = self.ix.L
         h = vp()
@@ -312,12 +394,46 @@ class DenseLachesis:
             None, BEGIN_BLOCK(self._begin), APPLY_EVENT(self._apply) if apply_events else APPLY_EVENT(),
             END_BLOCK(self._end))
         w = np.ascontiguousarray(weights, dtype=np.uint32)
-        rc = self.L.lx_abft_bootstrap(self.h, epoch, len(w), _p(w, u32p),
-                                      None if self._cb is None else ctypes.byref(self._cb))
-        if rc != 0:
-            raise LxError(rc, self.L.lx_abft_last_error(self.h).decode())
+        self.weights = w
+        if bootstrap:
+            rc = self.L.lx_abft_bootstrap(self.h, epoch, len(w), _p(w, u32p),
+                                          None if self._cb is None else ctypes.byref(self._cb))
+            if rc != 0:
+                raise LxError(rc, self.L.lx_abft_last_error(self.h).decode())
         if self.block_log:
             self.set_option("block_log", 2 if apply_events else 1)
+
+    def _chk(self, rc):
+        if rc != 0:
+            raise LxError(rc, self.L.lx_abft_last_error(self.h).decode())
+        return rc
+
+    def state(self):
+        """The abft state of the current epoch on dense indices
+        (lx_abft_state_fetch): ``epoch``, ``last_decided_frame``, ``ev_frame``,
+        ``ev_confirmed_on``, ``root_off``, ``root_ev``."""
+        return _fetch_state(self.L, self.h, self._chk)
+
+    def restore(self, state, creator, seq, poff, par, tables, chunk=4096):
+        """Resumes a persisted epoch on a handle created with
+        ``bootstrap=False``: reloads the index from ``tables`` -- what
+        :meth:`Index.writeback` returned at the epoch's flushes, merged:
+        {"S" / "s" / "b": {dense index: bytes}, "B": RLP(BranchesInfo)} -- for
+        the events given as to lx_add_batch, then lx_abft_restore."""
+        creator = np.ascontiguousarray(creator, dtype=np.uint32)
+        seq = np.ascontiguousarray(seq, dtype=np.uint32)
+        poff = np.ascontiguousarray(poff, dtype=np.uint64)
+        par = np.ascontiguousarray(par if len(par) else [0], dtype=np.uint32)
+        n = len(creator)
+        self.ix.reset(self.weights)
+        for lo in range(0, n, chunk):
+            hi = min(n, lo + chunk)
+            self.ix.load_rows(creator[lo:hi], seq[lo:hi], poff[lo:hi + 1] - poff[lo], par[int(poff[lo]):int(poff[hi])],
+                              b"".join(tables["b"][k] for k in range(lo, hi)),
+                              [tables["S"][k] for k in range(lo, hi)], [tables["s"][k] for k in range(lo, hi)])
+        if n or tables.get("B"):
+            self.ix.load_finish(tables.get("B", b""))
+        self._chk(restore_arrays(self.L, self.h, state, self.weights, creator, seq, poff, par, self._cb))
 
     def close(self):
         if getattr(self, "h", None):

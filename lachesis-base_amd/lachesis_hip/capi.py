@@ -115,6 +115,10 @@ SIGNATURES = [
     ("lx_abft_last_error", ctypes.c_char_p, [vp]),
     ("lx_abft_set_option", ctypes.c_int, [vp, ctypes.c_char_p, ctypes.c_int64]),
     ("lx_abft_bootstrap", ctypes.c_int, [vp, ctypes.c_uint32, ctypes.c_uint32, u32p, vp]),
+    ("lx_abft_restore", ctypes.c_int, [vp, ctypes.c_uint32, ctypes.c_uint32, u32p, ctypes.c_uint32, ctypes.c_uint32,
+                                       u32p, u32p, u64p, u32p, u32p, u32p, ctypes.c_uint32, u64p, u32p, vp]),
+    ("lx_abft_state_sizes", ctypes.c_int, [vp, vp]),
+    ("lx_abft_state_fetch", ctypes.c_int, [vp, u32p, u32p, u64p, u32p]),
     ("lx_abft_reset", ctypes.c_int, [vp, ctypes.c_uint32, ctypes.c_uint32, u32p]),
     ("lx_abft_process_batch", ctypes.c_int, [vp, ctypes.c_uint32, u32p, u32p, u64p, u32p, u32p, u32p, u32p]),
     ("lx_abft_build", ctypes.c_int, [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, u32p, u32p]),

@@ -129,6 +129,67 @@ def new_index_with_engine(crit, config, engine):
     return VecfcIndex(crit=crit, config=config, engine=engine)
 
 
+class InconsistentDB(RuntimeError):
+    """Persisted tables that do not form one epoch (the reference's crit,
+    vecengine/store_branches_info.go:83)."""
+
+
+def load_epoch_tables(ix, validators, db, get_event, order=None, chunk=4096):
+    """Reloads a freshly reset :class:`lachesis_hip.Index` from the persisted
+    tables "S" / "s" / "b" (keyed by event id) and "B" (lx_load_rows /
+    lx_load_finish) and returns the event ids in dense order.  ``order``: the
+    dense order to load in (parents first; the abft engine's restore keeps the
+    order its state was taken in); None: a parents-first order of table "b"'s
+    events.  Raises :class:`InconsistentDB`."""
+    from .capi import LxError
+    if order is None:
+        ids = list(db.get("b", {}))
+        if not ids and not db.get("B"):
+            return []                           # nothing flushed yet: an empty epoch
+        events = {eid: get_event(eid) for eid in ids}
+        order, state = [], {}
+        for root in sorted(ids, key=lambda x: (getattr(events[x], "lamport", 0), x)):
+            stack = [(root, False)]
+            while stack:
+                eid, done = stack.pop()
+                if done:
+                    if state.get(eid) != 2:
+                        state[eid] = 2
+                        order.append(eid)
+                    continue
+                if state.get(eid):
+                    continue
+                state[eid] = 1
+                stack.append((eid, True))
+                for p in reversed(events[eid].parents):
+                    if p not in events:
+                        raise InconsistentDB("inconsistent DB: parent %r of %r not persisted" % (p, eid))
+                    if not state.get(p):
+                        stack.append((p, False))
+    else:
+        order = list(order)
+        if not order and not db.get("B"):
+            return []
+        events = {eid: get_event(eid) for eid in order}
+    pos = {eid: k for k, eid in enumerate(order)}
+    try:
+        for lo in range(0, len(order), chunk):
+            part = order[lo:lo + chunk]
+            creator, seq, off, flat = [], [], [0], []
+            for eid in part:
+                e = events[eid]
+                creator.append(validators.idxs[e.creator])
+                seq.append(e.seq)
+                flat.extend(pos[p] for p in e.parents)
+                off.append(len(flat))
+            ix.load_rows(creator, seq, off, flat, b"".join(db["b"][eid] for eid in part),
+                         [db["S"][eid] for eid in part], [db["s"][eid] for eid in part])
+        ix.load_finish(db.get("B", {}).get(b"c", b""))
+    except (LxError, KeyError) as err:
+        raise InconsistentDB("inconsistent DB: %s" % (err,))
+    return order
+
+
 class _EngineState:
     """The epoch state a vecengine.Engine owns: the device handle, the event-ID
     <-> dense-index map, the flush point, validators and the getEvent
@@ -242,51 +303,14 @@ class VecfcIndex:
         RLP(BranchesInfo) (lx_load_rows / lx_load_finish) -- no replay of Add.
         Tables that do not form one consistent epoch call crit ("inconsistent
         DB", as vecengine/store_branches_info.go:83)."""
-        from .capi import LxError
         self.reset(validators, get_event)
-        ids = list(db.get("b", {}))
-        if not ids and not db.get("B"):
-            return                              # nothing flushed yet: an empty epoch
-        events = {eid: get_event(eid) for eid in ids}
-        order, state = [], {}
-        for root in sorted(ids, key=lambda x: (getattr(events[x], "lamport", 0), x)):
-            stack = [(root, False)]
-            while stack:
-                eid, done = stack.pop()
-                if done:
-                    if state.get(eid) != 2:
-                        state[eid] = 2
-                        order.append(eid)
-                    continue
-                if state.get(eid):
-                    continue
-                state[eid] = 1
-                stack.append((eid, True))
-                for p in reversed(events[eid].parents):
-                    if p not in events:
-                        self.crit(RuntimeError("inconsistent DB: parent %r of %r not persisted" % (p, eid)))
-                        return
-                    if not state.get(p):
-                        stack.append((p, False))
-        pos = {eid: k for k, eid in enumerate(order)}
         try:
-            for lo in range(0, len(order), chunk):
-                part = order[lo:lo + chunk]
-                creator, seq, off, flat = [], [], [0], []
-                for eid in part:
-                    e = events[eid]
-                    creator.append(validators.idxs[e.creator])
-                    seq.append(e.seq)
-                    flat.extend(pos[p] for p in e.parents)
-                    off.append(len(flat))
-                self.ix.load_rows(creator, seq, off, flat, b"".join(db["b"][eid] for eid in part),
-                                  [db["S"][eid] for eid in part], [db["s"][eid] for eid in part])
-            self.ix.load_finish(db.get("B", {}).get(b"c", b""))
-        except (LxError, KeyError) as err:
-            self.crit(RuntimeError("inconsistent DB: %s" % (err,)))
+            order = load_epoch_tables(self.ix, validators, db, get_event, chunk=chunk)
+        except InconsistentDB as err:
+            self.crit(err)
             return
         self.ids = order
-        self.pos = pos
+        self.pos = {eid: k for k, eid in enumerate(order)}
         self.n_flushed = len(order)
 
     def drop_not_flushed(self):
