@@ -26,6 +26,8 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "lachesis-base_amd")]
 CONFIGS = {
     "c4": (100, 1000, 10, 10, 10, "equal", 1),
     "c5": (1000, 50, 10, 0, 0, "zipf", 1),
+    # rows wider than 1024 columns (the root-FC kernels' ncols > 1024)
+    "w1100": (1100, 9, 10, 0, 0, "zipf", 1),
 }
 
 

@@ -265,13 +265,17 @@ def blocks_of(g):
 @pytest.mark.parametrize("name,chunks,fc16,claimed,blog", [("c4", 1, 1, 0, 0), ("c4", 7, 1, 0, 0), ("c5", 1, 1, 0, 0),
                                                            ("c5", 3, 1, 0, 0), ("c5", 1, 0, 0, 0), ("c4", 1, 1, 1, 0),
                                                            ("c4", 7, 1, 1, 0), ("c5", 1, 1, 1, 0), ("c5", 3, 0, 1, 0),
-                                                           ("c4", 7, 1, 1, 1), ("c5", 1, 1, 1, 1)])
+                                                           ("c4", 7, 1, 1, 1), ("c5", 1, 1, 1, 1),
+                                                           ("w1100", 1, 1, 0, 0), ("w1100", 3, 0, 1, 0),
+                                                           ("w1100", 1, 1, 1, 1)])
 def test_abft_full_size_vs_oracle(name, chunks, fc16, claimed, blog):
     """BASELINE configs 4 (100 validators, 10 % double-signers, 100k events)
     and 5 (1000 validators, Zipf stakes, 50k events) at full size: frames of
     every event, roots per frame and every block (Atropos, cheaters, ApplyEvent
     order) equal the C abft restatement's (tests/golden/make_abft_golden.py),
-    whole epoch in one batch or in chunks."""
+    whole epoch in one batch or in chunks.  w1100: 1100 validators x 9 events,
+    rows wider than 1024 columns through the root-FC kernels (packed and
+    32-bit)."""
     import numpy as np
     from lachesis_hip import abft, tools
     g = load_golden(name)

@@ -860,3 +860,102 @@ def test_la_memset_mode_matches(lx, opts):
         compare_rows(ix, o, range(len(d)))
         _all_pairs_fc(ix, o, len(d))
     ix.close()
+
+
+# ---------------------------------------------------------------- rows wider than 1024 columns
+# The ABI has no limit on V (only callers cap it); past 1024 columns the
+# ForklessCause kernels (k_fc<64>, k_fc_fk) and the row getters (get_row's
+# scan and chunked encode, the merged getter's creator chunks) run loops that
+# no narrower shape enters.
+WIDE_SHAPES = {
+    # name: (V, events/validator, parents, cheaters, forks, seed)
+    "v1025": (1025, 5, 10, 0, 0, 31),
+    "v1100": (1100, 6, 10, 0, 0, 32),
+    "v2100": (2100, 4, 10, 0, 0, 33),
+    "forks-b1095": (1000, 5, 10, 40, 4, 9),
+}
+_wide_cases = {}
+
+
+def wide_case(lx, name):
+    """The DAG of a wide shape with everything the oracle says about it,
+    computed once for both add paths."""
+    if name in _wide_cases:
+        return _wide_cases[name]
+    V, epv, p, ch, fk, seed = WIDE_SHAPES[name]
+    d = lx.tools.gen_dag(V, epv, p, cheaters=ch, forks=fk, seed=seed)
+    w = [(1 << 20) // (i + 1) for i in range(V)]
+    if ch:
+        w.reverse()                                           # the cheaters (first creators) hold little stake
+    o = oracle_for(d, w)
+    N = len(d)
+    ev = np.arange(N, dtype=np.uint32)
+    merged = [o.merged_hb(i) for i in range(N)]
+    moff = np.zeros(N + 1, dtype=np.uint64)
+    moff[1:] = np.cumsum([len(r) for r in merged])
+    rows = [o.rows(0, ev), o.rows(1, ev), (moff, np.frombuffer(b"".join(merged), dtype=np.uint8))]
+    branch = np.array([o.branch(i) for i in range(N)], dtype=np.uint32)
+    qa, qb = lx.tools.fc_queries(d.lamport, 100_000, seed=seed)
+    rng = np.random.default_rng(seed)
+    qa = np.concatenate([qa, rng.integers(0, N, 50_000).astype(np.uint32)])
+    qb = np.concatenate([qb, rng.integers(0, N, 50_000).astype(np.uint32)])
+    want = o.forkless_cause_batch_mt(qa, qb, 16)
+    assert 0.05 < want.mean() < 0.95
+    c = dict(d=d, w=w, B=o.num_branches(), rows=rows, branch=branch, qa=qa, qb=qb, want=want)
+    _wide_cases[name] = c
+    return c
+
+
+@pytest.mark.parametrize("name", list(WIDE_SHAPES))
+def test_wide_rows_end_to_end(lx, name):
+    """V (or B) beyond 1024: every HighestBefore, LowestAfter and merged row
+    byte-equal to the oracle, as one getter batch and in chunks of 64; branch
+    IDs and BranchesInfo; 150k ForklessCause pairs through the whole-row
+    kernel and (fork-free) the early exit with both lane widths; single-pair
+    calls (the result cache's row fills)."""
+    c = wide_case(lx, name)
+    d, w = c["d"], c["w"]
+    N, V = len(d), len(w)
+    ix = lx.Index()
+    ix.reset(w)
+    br = []
+    for lo in range(0, N, 2048):                              # batches the small path takes too
+        hi = min(N, lo + 2048)
+        br.extend(ix.add_batch(d.creator[lo:hi], d.seq[lo:hi], d.poff[lo:hi + 1], d.par, want_branches=True))
+    assert ix.num_branches() == c["B"] > 1024
+    assert np.array_equal(np.asarray(br, dtype=np.uint32), c["branch"])
+    last_seq, creator = ix.branches_info()
+    want_creator = np.zeros(c["B"], dtype=np.uint32)
+    want_creator[c["branch"]] = d.creator
+    want_last = np.zeros(c["B"], dtype=np.uint32)
+    np.maximum.at(want_last, c["branch"], d.seq)
+    assert np.array_equal(creator, want_creator) and np.array_equal(last_seq, want_last)
+    ev = np.arange(N, dtype=np.uint32)
+    for mode in (0, 1, 2):
+        ooff, obuf = c["rows"][mode]
+        if mode == 0:
+            assert int(np.diff(ooff).max()) > 8 * 1024        # rows encoded past column 1024
+        goff, gbuf = ix.rows_np(mode, ev)
+        np.testing.assert_array_equal(goff, ooff)
+        assert np.array_equal(gbuf, obuf), mode
+        for lo in range(0, N, 64):
+            goff, gbuf = ix.rows_np(mode, ev[lo:lo + 64])
+            np.testing.assert_array_equal(goff, ooff[lo:lo + 65] - ooff[lo])
+            assert np.array_equal(gbuf, obuf[int(ooff[lo]):int(ooff[min(N, lo + 64)])]), (mode, lo)
+    for i in (0, N // 2, N - 1):                              # the single-row getters
+        ooff, obuf = c["rows"][0]
+        assert ix.highest_before(i) == obuf[int(ooff[i]):int(ooff[i + 1])].tobytes()
+        ooff, obuf = c["rows"][2]
+        assert ix.merged_highest_before(i) == obuf[int(ooff[i]):int(ooff[i + 1])].tobytes()
+    qa, qb, want = c["qa"], c["qb"], c["want"]
+    for lanes in (32, 16):
+        ix.set_option("fc_early_lanes", lanes)
+        ix.fc_early_rounds()
+        np.testing.assert_array_equal(ix.forkless_cause_batch(qa, qb), want)
+        # Zipf stakes: the early path takes every fork-free launch of this size
+        assert ix.fc_early_rounds()[0] == (len(qa) if c["B"] == V else 0)
+    ix.set_option("fc_early", 0)
+    np.testing.assert_array_equal(ix.forkless_cause_batch(qa, qb), want)
+    assert ix.fc_early_rounds()[0] == 0
+    assert [ix.forkless_cause(int(a), int(b)) for a, b in zip(qa[:300], qb[:300])] == [bool(x) for x in want[:300]]
+    ix.close()
