@@ -74,6 +74,8 @@ const char *lx_last_error(const lx_index *h);
  *   "cpw"        walker columns per workgroup: 0 (auto), 1, 2, 4, 8 or 12 (8, 12: packed
  *                fork-free epochs, else 4; 12: whole handles, a sharded one walks 8)
  *   "pack16"     0: two slot units per event even when every seq fits 16 bits
+ *   "fold3"      0: the 8- / 12-column packed walks fold by two-input integer maxima even
+ *                when every seq of the epoch is <= 0x7BFF (default 1: three-input maxima there)
  *   "crec"       1: the 8- / 12-column walks stream 32-B compact event records instead of
  *                the 64-B ones (fork-free epochs, 16-bit branches and seqs)
  *   "fc_early_lanes" 32 (default) or 16 lanes per query in the early-exit ForklessCause

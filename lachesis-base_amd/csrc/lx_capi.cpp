@@ -727,6 +727,7 @@ int add_batch_dev(lx_index *h, uint32_t n, const uint32_t *creator, const uint32
     ia.mask = (h->B > h->V) ? 1u : 0u;
     ia.cpw_hint = h->cpw_hint;
     ia.pack16 = h->pack16 && h->max_seq <= 0xFFFFu;
+    ia.fold3 = ia.pack16 && h->fold3 && h->max_seq <= kFold3MaxSeq;
     ia.seg_xmap = h->seg_xmap_opt ? 1u : 0u;
     if (ia.cpw_hint >= 8 && (!ia.pack16 || ia.mask)) ia.cpw_hint = 4;   // 8- / 12-column slots: packed, fork-free
     const size_t prof_n = (size_t)kProfBlocks * kProfWaves * kProfSlots;
@@ -1888,6 +1889,8 @@ int lx_set_option(lx_index *h, const char *name, int64_t value) {
         h->cpw_hint = (uint32_t)value;
     } else if (k == "pack16") {
         h->pack16 = value != 0;
+    } else if (k == "fold3") {
+        h->fold3 = value != 0;
     } else if (k == "crec") {
         h->crec_opt = value != 0;
     } else if (k == "seg_xmap") {

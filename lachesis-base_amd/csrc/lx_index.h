@@ -259,6 +259,7 @@ struct lx_index {
     bool small_timing = false;             // option timing=1: time small-path launches (two event records)
     uint32_t cpw_hint = 0;                 // option cpw: walker columns per workgroup (0 = auto)
     bool pack16 = true;                    // option pack16=0: two slot units per event even for small seqs
+    bool fold3 = true;                     // option fold3=0: the integer fold even when every seq <= kFold3MaxSeq
     bool seg_xmap_opt = false;             // option seg_xmap=1: 12-column walks keep each HB line's slices on one XCD
     bool crec_opt = false;                 // option crec=1: the 8- / 12-column walks stream the 32-B compact records
     bool prof = false;                     // LX_PROF=1 in make WPROF=1 builds: per-wave walker counters

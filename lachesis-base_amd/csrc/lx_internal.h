@@ -55,6 +55,19 @@ struct CRec {
 };
 constexpr uint32_t kCrecWide = 0xFFFFFFFFu;
 
+// Three-input packed 16-bit maximum (the F3 fold of the 8- / 12-column packed
+// walks; tests/csrc/fold3_harness.cpp checks it against the integer maximum).
+// v_pk_maximum3_f16 on raw seq words: for the bit patterns 0x0000..kFold3MaxSeq
+// (non-negative finite f16, denormals kept: hipcc's default f16 denormal mode)
+// IEEE order is unsigned-integer order, so on words whose halves all lie in
+// that range it computes the same function as two v_pk_max_u16
+constexpr uint32_t kFold3MaxSeq = 0x7BFFu;
+__device__ __forceinline__ uint32_t pk_max3_f16(uint32_t a, uint32_t b, uint32_t c) {
+    uint32_t d;
+    asm("v_pk_maximum3_f16 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
+    return d;
+}
+
 constexpr uint32_t kSegLaunchMax = 32;   // segments of one k_index_segs launch
 struct IndexArgs {
     uint32_t *hb;
@@ -82,6 +95,8 @@ struct IndexArgs {
     uint32_t *lap;               // sharded: LowestAfter rows of own branches (fill target)
     uint64_t lap_stride;         // = global branch capacity
     uint32_t pack16;             // every seq of the epoch <= 0xFFFF: 16-B packed slots (4-column block walker)
+    uint32_t fold3;              // pack16 and every seq of the epoch <= kFold3MaxSeq: the three-input fold
+                                 // (8- / 12-column packed walks; option fold3 = 0 forces the integer fold)
     // segment walk (lx_segment.hip): parents before batch_start contribute only
     // their own (branch, seq) entry, and no LowestAfter is filled
     uint32_t seg;

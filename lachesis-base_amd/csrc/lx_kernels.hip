@@ -605,9 +605,11 @@ __device__ __forceinline__ void blk_fold(const uint32_t pa[3], uint32_t W, uint3
 // (B > V); PK: 4-column slices with 16-bit packed slot units (every seq of the
 // epoch <= 0xFFFF).
 // CR: the compact records (CRec) of 8- / 12-column packed walks
-template <int CPW, int NCW, bool MASKED, bool PK, int ND_ = kND, bool CR = false>
+// F3: the SPLIT fold by three-input packed maxima (pk_max3_f16: every seq of the epoch <= kFold3MaxSeq)
+template <int CPW, int NCW, bool MASKED, bool PK, int ND_ = kND, bool CR = false, bool F3 = false>
 __device__ __forceinline__ void index_body(const IndexArgs &a, const uint32_t slice) {
     static_assert(!PK || CPW >= 4, "packed slots: 4-, 8- or 12-column slices");
+    static_assert(!F3 || (PK && CPW >= 8 && !CR), "three-input fold: 8- / 12-column packed walks, full records");
     static_assert(!CR || (PK && CPW >= 8), "compact records: 8- / 12-column packed walks");
     static_assert(CPW == 1 || CPW == 2 || CPW == 4 || ((CPW == 8 || CPW == 12) && PK && !MASKED), "slot layout");
     static_assert(LX_MAXP == 12, "block walker: 12 inline parents, three per lane of a quad");
@@ -1018,7 +1020,7 @@ __device__ __forceinline__ void index_body(const IndexArgs &a, const uint32_t sl
                 if ((uint32_t)k == j + 4) { mycol2 = col(k); myvalid2 = valid(k); }
         }
         uint32_t blk = __builtin_amdgcn_readfirstlane(wave);   // wave-uniform: scalar loop control
-        bool loaded = false, done = true;
+        bool done = true;
         uint32_t br = 0, seq = 0, np = 0, xi = 0;
         bool wxi = false;   // some event of the wave's block has parents beyond the inline twelve (wave-uniform)
         uint32_t wstuck = 0;   // passes since the block fetch (wave-uniform)
@@ -1028,7 +1030,9 @@ __device__ __forceinline__ void index_body(const IndexArgs &a, const uint32_t sl
         // one DPP step (lanes j, j ^ 2) instead of two, with no unit selects at
         // the publish: ~45 VALU per pass instead of ~70, C3 walk 47.1 -> 43.4 ms
         // (same six 16-B LDS reads per lane); otherwise lane j reads both units
-        // of parents j + 4i, i < 3
+        // of parents j + 4i, i < 3.  F3 folds a word's seven operands by three
+        // three-input maxima instead of six two-input ones (~39 VALU per pass,
+        // C3 walk 94.2M -> 85.9M cycles)
         constexpr bool SPLIT = PK && CPW >= 8;
         constexpr int NPL = SPLIT ? 6 : 3;   // parent slots per lane
         const uint32_t uoff = (SPLIT && (j & 1)) ? (uint32_t)(RN + 1) * 16u : 0u;   // unit B array
@@ -1092,10 +1096,10 @@ __device__ __forceinline__ void index_body(const IndexArgs &a, const uint32_t sl
         const unsigned long long t_start = wall_clock64();
 #endif
         while (blk * 16 < n) {
-            LX_WP(c_pass++;)
             const uint32_t lp = blk * 16 + quad;
             const bool live = lp < n;
-            if (!loaded) {
+            {
+                // block fetch (until the loader has landed the block's records)
                 const uint32_t slot = lp % RR;
                 const uint32_t ra = lds_addr(rrec) + rec_off<RQ>(slot, 0) * 16u;
                 uint32_t tg, w[NPL];
@@ -1163,6 +1167,7 @@ __device__ __forceinline__ void index_body(const IndexArgs &a, const uint32_t sl
                         : "memory");
                 }
                 if (!__all(!live || tg == lp / 64 + 1)) {
+                    LX_WP(c_pass++;)
                     LX_WP(c_norec++;)
                     continue;   // wave-uniform: the loader is behind
                 }
@@ -1231,7 +1236,6 @@ __device__ __forceinline__ void index_body(const IndexArgs &a, const uint32_t sl
                     wm_addr = lds_addr(&sh.copied[rr % ND]);
                 }
                 done = !live;
-                loaded = true;
                 repack(true);
 #ifdef LX_WALKER_PROF
                 {
@@ -1247,191 +1251,201 @@ __device__ __forceinline__ void index_body(const IndexArgs &a, const uint32_t sl
                 }
 #endif
             }
-            // fold (published quads read the null slot).  No per-parent select:
-            // the quad publishes only in a pass where all twelve of its slot
-            // reads carried the expected tags, so that pass's unconditional
-            // max over them is the event's value; r holds only what does not
-            // come from the ring (own seq, L2 rows of old / overflow parents)
-            uint32_t tg[NPL][2], pv[3][CPW];
-            u4v xs[SPLIT ? NPL : 1];   // SPLIT: the lane's six units
-            uint32_t tx = 0;
-            if constexpr (SPLIT) {
-                asm volatile(
-                    "ds_read_b128 %0, %7\n\t"
-                    "ds_read_b128 %1, %8\n\t"
-                    "ds_read_b128 %2, %9\n\t"
-                    "ds_read_b128 %3, %10\n\t"
-                    "ds_read_b128 %4, %11\n\t"
-                    "ds_read_b128 %5, %12\n\t"
-                    "ds_read_b32 %6, %13\n\t"
-                    "s_waitcnt lgkmcnt(0)"
-                    : "=&v"(xs[0]), "=&v"(xs[1 % NPL]), "=&v"(xs[2 % NPL]), "=&v"(xs[3 % NPL]), "=&v"(xs[4 % NPL]),
-                      "=&v"(xs[5 % NPL]), "=&v"(cw)
-                    : "v"(pa[0]), "v"(pa[1 % NPL]), "v"(pa[2 % NPL]), "v"(pa[3 % NPL]), "v"(pa[4 % NPL]),
-                      "v"(pa[5 % NPL]), "v"(wm_addr)
-                    : "memory");
+            // passes over the block until all its 16 quads have published
+            do {
+                LX_WP(c_pass++;)
+                // fold (published quads read the null slot).  No per-parent select:
+                // the quad publishes only in a pass where all twelve of its slot
+                // reads carried the expected tags, so that pass's unconditional
+                // max over them is the event's value; r holds only what does not
+                // come from the ring (own seq, L2 rows of old / overflow parents)
+                uint32_t tg[NPL][2], pv[3][CPW];
+                u4v xs[SPLIT ? NPL : 1];   // SPLIT: the lane's six units
+                uint32_t tx = 0;
+                if constexpr (SPLIT) {
+                    asm volatile(
+                        "ds_read_b128 %0, %7\n\t"
+                        "ds_read_b128 %1, %8\n\t"
+                        "ds_read_b128 %2, %9\n\t"
+                        "ds_read_b128 %3, %10\n\t"
+                        "ds_read_b128 %4, %11\n\t"
+                        "ds_read_b128 %5, %12\n\t"
+                        "ds_read_b32 %6, %13\n\t"
+                        "s_waitcnt lgkmcnt(0)"
+                        : "=&v"(xs[0]), "=&v"(xs[1 % NPL]), "=&v"(xs[2 % NPL]), "=&v"(xs[3 % NPL]), "=&v"(xs[4 % NPL]),
+                          "=&v"(xs[5 % NPL]), "=&v"(cw)
+                        : "v"(pa[0]), "v"(pa[1 % NPL]), "v"(pa[2 % NPL]), "v"(pa[3 % NPL]), "v"(pa[4 % NPL]),
+                          "v"(pa[5 % NPL]), "v"(wm_addr)
+                        : "memory");
 #pragma unroll
-                for (int k = 0; k < NPL; k++) { tg[k][0] = tg[k][1] = xs[k].x; tx |= xs[k].x ^ px[k]; }
-            } else {
-                blk_fold<CPW, RN, PK>(pa, wm_addr, tg, pv, cw);
-                // tag mismatches OR-ed on the VALU: no compare masks and no mask
-                // ANDs on the scalar unit, which the CU's waves share (C3 -1.9 %,
-                // C2 -5.2 % against v_cmp + s_and)
-#pragma unroll
-                for (int k = 0; k < 3; k++) tx |= (tg[k][0] ^ px[k]) | ((PK && CPW == 4) || CPW < 4 ? 0u : (tg[k][1] ^ px[k]));
-            }
-            // the quad's readiness: its four lanes' mismatches OR-ed by DPP
-            // (two VALU steps; the ballot / scalar-shift / per-lane bit test it
-            // replaced cost 7 VALU and 3 SALU: C3 walk -3.4 %)
-            tx |= (uint32_t)__builtin_amdgcn_mov_dpp((int)tx, kQuadSwap1, 0xF, 0xF, true);
-            tx |= (uint32_t)__builtin_amdgcn_mov_dpp((int)tx, kQuadSwap2, 0xF, 0xF, true);
-            const bool rdy = tx == 0u;   // all twelve slot tags of the quad as expected
-            uint32_t m[CPW];
-            uint32_t mp[NH];   // PK: the quad's maxima, two columns per dword
-#pragma unroll
-            for (int h = 0; h < NH; h++) mp[h] = 0u;
-            if constexpr (SPLIT) {
-                // the lane's unit over its six parents, then lanes j and j ^ 2
-                // (same unit, the other parents): mp[0..2] = the event's unit
-#pragma unroll
-                for (int d = 0; d < 3; d++) {
-                    uint32_t v[NPL];
-#pragma unroll
-                    for (int k = 0; k < NPL; k++) v[k] = d == 0 ? xs[k].y : d == 1 ? xs[k].z : xs[k].w;
-                    const uint32_t t = pk_max(pk_max(pk_max(rpk[d], v[0]), pk_max(v[1 % NPL], v[2 % NPL])),
-                                              pk_max(pk_max(v[3 % NPL], v[4 % NPL]), v[5 % NPL]));
-                    mp[d] = pk_max(t, (uint32_t)__builtin_amdgcn_mov_dpp((int)t, kQuadSwap2, 0xF, 0xF, true));
-                }
-            } else if constexpr (PK) {
-                // two columns per dword: three packed maxima per dword, the quad
-                // reduction on packed words
-#pragma unroll
-                for (int h = 0; h < NH; h++) {
-                    const uint32_t rp = rpk[h];
-                    mp[h] = quad_pk_max(pk_max(pk_max(rp, pv[0][h % CPW]), pk_max(pv[1][h % CPW], pv[2][h % CPW])));
-                }
-            } else {
-#pragma unroll
-                for (int c = 0; c < CPW; c++) {
-                    uint32_t t;
-                    asm("v_max3_u32 %0, %1, %2, %3" : "=v"(t) : "v"(r[c]), "v"(pv[0][c]), "v"(pv[1][c]));
-                    m[c] = quad_max(max(t, pv[2][c]));
-                }
-            }
-            if (wxi && rdy && !done && xi < np) {   // (the scalar test first: most blocks have none)
-                // parents beyond the inline twelve (rare): one per pass, the same on every lane of the quad
-                const uint32_t pg = ld_l2_now(a.par_in + a.poff_in[lp] + xi);
-                const uint32_t lpp = pg - bs;
-                bool ok = false, old = lpp >= n;
-                if (!old) {
-                    Slot<CPW> ps;
-                    ring_read1<CPW, PK>(RA, RB, lpp % RN, ps);
-                    if (ps.t0 == lpp + 1 && ps.t1 == lpp + 1) {
-#pragma unroll
-                        for (int c = 0; c < CPW; c++) addcol(c, ps.v[c]);
-                        ok = true;
-                    } else if (max(ps.t0, ps.t1) > lpp + 1) {
-                        if (round_done<ND>(sh.stored, lpp)) old = true;
-                        else __hip_atomic_store(&sh.req, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    }
-                }
-                if (old && a.seg && lpp >= n) {
-                    const uint32_t pb = a.ev_branch[pg], ps = a.ev_seq[pg];
-#pragma unroll
-                    for (int c = 0; c < CPW; c++)
-                        if (valid(c) && col(c) == pb) addcol(c, ps);
-                    ok = true;
-                } else if (old) {
-                    const uint32_t *row = a.hb + (uint64_t)pg * stride;
-#pragma unroll
-                    for (int c = 0; c < CPW; c++)
-                        if (valid(c)) addcol(c, ld_l2_now(row + pc(c)) & mask);
-                    ok = true;
-                }
-                // the same parent on every lane of the quad: m stays the quad's value
-                if constexpr (PK) {
-                    repack(false);
-#pragma unroll
-                    for (int h = 0; h < (SPLIT ? 3 : NH); h++) mp[h] = pk_max(mp[h], rpk[h]);
+                    for (int k = 0; k < NPL; k++) { tg[k][0] = tg[k][1] = xs[k].x; tx |= xs[k].x ^ px[k]; }
                 } else {
+                    blk_fold<CPW, RN, PK>(pa, wm_addr, tg, pv, cw);
+                    // tag mismatches OR-ed on the VALU: no compare masks and no mask
+                    // ANDs on the scalar unit, which the CU's waves share (C3 -1.9 %,
+                    // C2 -5.2 % against v_cmp + s_and)
 #pragma unroll
-                    for (int c = 0; c < CPW; c++) m[c] = max(m[c], r[c]);
+                    for (int k = 0; k < 3; k++) tx |= (tg[k][0] ^ px[k]) | ((PK && CPW == 4) || CPW < 4 ? 0u : (tg[k][1] ^ px[k]));
                 }
-                if (quad_and(ok ? 1u : 0u)) xi++;
-            }
-            {
-                // publish, branch-free: a ready quad whose slot's previous
-                // occupant (lp - RN) is drained (as of this pass's watermark)
-                // writes unit A from lane 0 and unit B from lane 1, and its
-                // recent-event entry; every other lane writes the same
-                // instructions into its own dummy slot
-                const bool fin = rdy && !done && xi >= np && cw >= wneed;
-                const uint32_t wa = fin ? wa_pub : dmy;
-                const uint32_t wb = fin ? wb_pub : dmy + 1024u;
-                u2v y;
-                y.x = seq; y.y = bs + lp;
-                if constexpr (CPW == 1) {
-                    u2v x;
-                    x.x = lp + 1; x.y = m[0];
-                    asm volatile("ds_write_b64 %2, %3\n\tds_write_b64 %0, %1" : : "v"(wa), "v"(x), "v"(wb), "v"(y) : "memory");
-                } else if constexpr (PK && CPW >= 8) {
-                    u4v x;   // lane 0: {tag, s01, s23, s45}, lane 1: {tag, s67, 0, 0} (12: {tag, s67, s89, s1011})
-                    x.x = lp + 1;
-                    if constexpr (SPLIT) {
-                        x.y = mp[0]; x.z = mp[1 % NH]; x.w = mp[2 % NH];
-                    } else {
-                        x.y = j == 0 ? mp[0] : mp[3 % NH];
-                        x.z = j == 0 ? mp[1 % NH] : CPW == 12 ? mp[4 % NH] : 0u;
-                        x.w = j == 0 ? mp[2 % NH] : CPW == 12 ? mp[5 % NH] : 0u;
+                // the quad's readiness: its four lanes' mismatches OR-ed by DPP
+                // (two VALU steps; the ballot / scalar-shift / per-lane bit test it
+                // replaced cost 7 VALU and 3 SALU: C3 walk -3.4 %)
+                tx |= (uint32_t)__builtin_amdgcn_mov_dpp((int)tx, kQuadSwap1, 0xF, 0xF, true);
+                tx |= (uint32_t)__builtin_amdgcn_mov_dpp((int)tx, kQuadSwap2, 0xF, 0xF, true);
+                const bool rdy = tx == 0u;   // all twelve slot tags of the quad as expected
+                uint32_t m[CPW];
+                uint32_t mp[NH];   // PK: the quad's maxima, two columns per dword
+#pragma unroll
+                for (int h = 0; h < NH; h++) mp[h] = 0u;
+                if constexpr (SPLIT) {
+                    // the lane's unit over its six parents, then lanes j and j ^ 2
+                    // (same unit, the other parents): mp[0..2] = the event's unit
+#pragma unroll
+                    for (int d = 0; d < 3; d++) {
+                        uint32_t v[NPL];
+#pragma unroll
+                        for (int k = 0; k < NPL; k++) v[k] = d == 0 ? xs[k].y : d == 1 ? xs[k].z : xs[k].w;
+                        uint32_t t;
+                        if constexpr (F3) {
+                            // seven operands in three instructions instead of six
+                            // (rpk may come from the integer maxima of the rare
+                            // paths: the same function on seqs <= kFold3MaxSeq)
+                            t = pk_max3_f16(pk_max3_f16(rpk[d], v[0], v[1 % NPL]),
+                                            pk_max3_f16(v[2 % NPL], v[3 % NPL], v[4 % NPL]), v[5 % NPL]);
+                        } else {
+                            t = pk_max(pk_max(pk_max(rpk[d], v[0]), pk_max(v[1 % NPL], v[2 % NPL])),
+                                       pk_max(pk_max(v[3 % NPL], v[4 % NPL]), v[5 % NPL]));
+                        }
+                        mp[d] = pk_max(t, (uint32_t)__builtin_amdgcn_mov_dpp((int)t, kQuadSwap2, 0xF, 0xF, true));
                     }
-                    asm volatile("ds_write_b64 %2, %3\n\tds_write_b128 %0, %1" : : "v"(wa), "v"(x), "v"(wb), "v"(y) : "memory");
                 } else if constexpr (PK) {
-                    u4v x;   // lane 0: {tag, s0 | s1 << 16, s2 | s3 << 16, 0}
-                    x.x = lp + 1; x.y = mp[0]; x.z = mp[1 % NH]; x.w = 0u;
-                    asm volatile("ds_write_b64 %2, %3\n\tds_write_b128 %0, %1" : : "v"(wa), "v"(x), "v"(wb), "v"(y) : "memory");
-                } else {
-                    u4v x;
-                    x.x = lp + 1; x.y = j == 0 ? m[0] : m[3 % CPW]; x.z = j == 0 ? m[1 % CPW] : 0u;
-                    x.w = (CPW == 4 && j == 0) ? m[2 % CPW] : 0u;
-                    asm volatile("ds_write_b64 %2, %3\n\tds_write_b128 %0, %1" : : "v"(wa), "v"(x), "v"(wb), "v"(y) : "memory");
-                }
-                LX_WP(c_done += fin ? 1u : 0u;)
-                LX_WP(c_wm += (rdy && !done && !fin) ? 1u : 0u;)
-                done = done || fin;
-                // a published quad reads the null slot from now on: one
-                // address for all its lanes, a broadcast instead of twelve
-                // scattered 16-B reads in the passes its wave still makes
-                // (C3 walk -2 %)
+                    // two columns per dword: three packed maxima per dword, the quad
+                    // reduction on packed words
 #pragma unroll
-                for (int k = 0; k < NPL; k++) pa[k] = done ? ANUL : pa[k];
-            }
-            if (++wstuck >= kLeanStuck && !rdy && !done) {
-                // waiting long (the wave's block fetched >= 64 passes ago): a
-                // parent's slot may have been reused by a newer event; its HB
-                // row from L2 once its drain stored it
-#pragma unroll
-                for (int k = 0; k < NPL; k++) {
-                    const uint32_t x = px[k];
-                    if (x == kNullTag || (tg[k][0] == x && tg[k][1] == x) || max(tg[k][0], tg[k][1]) <= x) continue;
-                    if (!round_done<ND>(sh.stored, x - 1u)) {
-                        LX_WP(c_wm++;)
-                        __hip_atomic_store(&sh.req, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                        continue;
+                    for (int h = 0; h < NH; h++) {
+                        const uint32_t rp = rpk[h];
+                        mp[h] = quad_pk_max(pk_max(pk_max(rp, pv[0][h % CPW]), pk_max(pv[1][h % CPW], pv[2][h % CPW])));
                     }
-                    LX_WP(c_slow++;)
-                    const uint32_t *row = a.hb + (uint64_t)(x - 1u + bs) * stride;
+                } else {
 #pragma unroll
-                    for (int c = 0; c < CPW; c++)
-                        if (valid(c)) addcol(c, ld_l2_now(row + pc(c)) & mask);
-                    px[k] = kNullTag;
-                    pa[k] = ANUL;
+                    for (int c = 0; c < CPW; c++) {
+                        uint32_t t;
+                        asm("v_max3_u32 %0, %1, %2, %3" : "=v"(t) : "v"(r[c]), "v"(pv[0][c]), "v"(pv[1][c]));
+                        m[c] = quad_max(max(t, pv[2][c]));
+                    }
                 }
-                repack(false);
-            }
-            if (__all(done)) {
-                blk += NCW;
-                loaded = false;
-            }
+                if (wxi && rdy && !done && xi < np) {   // (the scalar test first: most blocks have none)
+                    // parents beyond the inline twelve (rare): one per pass, the same on every lane of the quad
+                    const uint32_t pg = ld_l2_now(a.par_in + a.poff_in[lp] + xi);
+                    const uint32_t lpp = pg - bs;
+                    bool ok = false, old = lpp >= n;
+                    if (!old) {
+                        Slot<CPW> ps;
+                        ring_read1<CPW, PK>(RA, RB, lpp % RN, ps);
+                        if (ps.t0 == lpp + 1 && ps.t1 == lpp + 1) {
+#pragma unroll
+                            for (int c = 0; c < CPW; c++) addcol(c, ps.v[c]);
+                            ok = true;
+                        } else if (max(ps.t0, ps.t1) > lpp + 1) {
+                            if (round_done<ND>(sh.stored, lpp)) old = true;
+                            else __hip_atomic_store(&sh.req, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        }
+                    }
+                    if (old && a.seg && lpp >= n) {
+                        const uint32_t pb = a.ev_branch[pg], ps = a.ev_seq[pg];
+#pragma unroll
+                        for (int c = 0; c < CPW; c++)
+                            if (valid(c) && col(c) == pb) addcol(c, ps);
+                        ok = true;
+                    } else if (old) {
+                        const uint32_t *row = a.hb + (uint64_t)pg * stride;
+#pragma unroll
+                        for (int c = 0; c < CPW; c++)
+                            if (valid(c)) addcol(c, ld_l2_now(row + pc(c)) & mask);
+                        ok = true;
+                    }
+                    // the same parent on every lane of the quad: m stays the quad's value
+                    if constexpr (PK) {
+                        repack(false);
+#pragma unroll
+                        for (int h = 0; h < (SPLIT ? 3 : NH); h++) mp[h] = pk_max(mp[h], rpk[h]);
+                    } else {
+#pragma unroll
+                        for (int c = 0; c < CPW; c++) m[c] = max(m[c], r[c]);
+                    }
+                    if (quad_and(ok ? 1u : 0u)) xi++;
+                }
+                {
+                    // publish, branch-free: a ready quad whose slot's previous
+                    // occupant (lp - RN) is drained (as of this pass's watermark)
+                    // writes unit A from lane 0 and unit B from lane 1, and its
+                    // recent-event entry; every other lane writes the same
+                    // instructions into its own dummy slot
+                    const bool fin = rdy && !done && xi >= np && cw >= wneed;
+                    const uint32_t wa = fin ? wa_pub : dmy;
+                    const uint32_t wb = fin ? wb_pub : dmy + 1024u;
+                    u2v y;
+                    y.x = seq; y.y = bs + lp;
+                    if constexpr (CPW == 1) {
+                        u2v x;
+                        x.x = lp + 1; x.y = m[0];
+                        asm volatile("ds_write_b64 %2, %3\n\tds_write_b64 %0, %1" : : "v"(wa), "v"(x), "v"(wb), "v"(y) : "memory");
+                    } else if constexpr (PK && CPW >= 8) {
+                        u4v x;   // lane 0: {tag, s01, s23, s45}, lane 1: {tag, s67, 0, 0} (12: {tag, s67, s89, s1011})
+                        x.x = lp + 1;
+                        if constexpr (SPLIT) {
+                            x.y = mp[0]; x.z = mp[1 % NH]; x.w = mp[2 % NH];
+                        } else {
+                            x.y = j == 0 ? mp[0] : mp[3 % NH];
+                            x.z = j == 0 ? mp[1 % NH] : CPW == 12 ? mp[4 % NH] : 0u;
+                            x.w = j == 0 ? mp[2 % NH] : CPW == 12 ? mp[5 % NH] : 0u;
+                        }
+                        asm volatile("ds_write_b64 %2, %3\n\tds_write_b128 %0, %1" : : "v"(wa), "v"(x), "v"(wb), "v"(y) : "memory");
+                    } else if constexpr (PK) {
+                        u4v x;   // lane 0: {tag, s0 | s1 << 16, s2 | s3 << 16, 0}
+                        x.x = lp + 1; x.y = mp[0]; x.z = mp[1 % NH]; x.w = 0u;
+                        asm volatile("ds_write_b64 %2, %3\n\tds_write_b128 %0, %1" : : "v"(wa), "v"(x), "v"(wb), "v"(y) : "memory");
+                    } else {
+                        u4v x;
+                        x.x = lp + 1; x.y = j == 0 ? m[0] : m[3 % CPW]; x.z = j == 0 ? m[1 % CPW] : 0u;
+                        x.w = (CPW == 4 && j == 0) ? m[2 % CPW] : 0u;
+                        asm volatile("ds_write_b64 %2, %3\n\tds_write_b128 %0, %1" : : "v"(wa), "v"(x), "v"(wb), "v"(y) : "memory");
+                    }
+                    LX_WP(c_done += fin ? 1u : 0u;)
+                    LX_WP(c_wm += (rdy && !done && !fin) ? 1u : 0u;)
+                    done = done || fin;
+                    // a published quad reads the null slot from now on: one
+                    // address for all its lanes, a broadcast instead of twelve
+                    // scattered 16-B reads in the passes its wave still makes
+                    // (C3 walk -2 %)
+#pragma unroll
+                    for (int k = 0; k < NPL; k++) pa[k] = done ? ANUL : pa[k];
+                }
+                if (++wstuck >= kLeanStuck && !rdy && !done) {
+                    // waiting long (the wave's block fetched >= 64 passes ago): a
+                    // parent's slot may have been reused by a newer event; its HB
+                    // row from L2 once its drain stored it
+#pragma unroll
+                    for (int k = 0; k < NPL; k++) {
+                        const uint32_t x = px[k];
+                        if (x == kNullTag || (tg[k][0] == x && tg[k][1] == x) || max(tg[k][0], tg[k][1]) <= x) continue;
+                        if (!round_done<ND>(sh.stored, x - 1u)) {
+                            LX_WP(c_wm++;)
+                            __hip_atomic_store(&sh.req, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                            continue;
+                        }
+                        LX_WP(c_slow++;)
+                        const uint32_t *row = a.hb + (uint64_t)(x - 1u + bs) * stride;
+#pragma unroll
+                        for (int c = 0; c < CPW; c++)
+                            if (valid(c)) addcol(c, ld_l2_now(row + pc(c)) & mask);
+                        px[k] = kNullTag;
+                        pa[k] = ANUL;
+                    }
+                    repack(false);
+                }
+            } while (!__all(done));
+            blk += NCW;
         }
 #ifdef LX_WALKER_PROF
         if (a.prof) {
@@ -1478,13 +1492,13 @@ struct WalkClock {
     }
 };
 
-template <int CPW, int NCW, bool MASKED, bool PK, int ND = kND, bool CR = false>
+template <int CPW, int NCW, bool MASKED, bool PK, int ND = kND, bool CR = false, bool F3 = false>
 __global__ __launch_bounds__(64 * (NCW + 1 + ND)) void k_index(IndexArgs a) {
     WalkClock wc;
     wc.start();
     // XCD-aware: neighbouring slices share an L2
     const uint32_t slice = (blockIdx.x % 8) * a.slices_per_xcd + blockIdx.x / 8;
-    index_body<CPW, NCW, MASKED, PK, ND, CR>(a, slice);
+    index_body<CPW, NCW, MASKED, PK, ND, CR, F3>(a, slice);
     wc.stop(a.clk, slice < a.n_slices);
 }
 
@@ -1517,7 +1531,7 @@ __device__ __forceinline__ bool seg_chunk(uint32_t g, uint32_t G, uint32_t S, ui
 // blockIdx.x walks segment blockIdx.x / (gridDim.x / seg_g) with the
 // segment's own batch window, J table and partial-event lists (lx_segment.hip)
 
-template <int CPW, int NCW, bool MASKED, bool PK, int ND = kND, bool CR = false>
+template <int CPW, int NCW, bool MASKED, bool PK, int ND = kND, bool CR = false, bool F3 = false>
 __global__ __launch_bounds__(64 * (NCW + 1 + ND)) void k_index_segs(IndexArgs a0) {
     WalkClock wc;
     wc.start();
@@ -1555,7 +1569,7 @@ __global__ __launch_bounds__(64 * (NCW + 1 + ND)) void k_index_segs(IndexArgs a0
 #ifdef LX_PROBE_SKEW
     if (threadIdx.x == 0 && blockIdx.x < 1024) g_probe_map[blockIdx.x] = k << 16 | slice;
 #endif
-    index_body<CPW, NCW, MASKED, PK, ND, CR>(a, slice);
+    index_body<CPW, NCW, MASKED, PK, ND, CR, F3>(a, slice);
     wc.stop(a0.clk, slice < a.n_slices);
 }
 
@@ -1600,6 +1614,9 @@ static hipError_t launch_index_t(const IndexArgs &a0, hipStream_t s) {
         // compact records when the batch wrote them (fork-free, 16-bit branches and seqs)
         if (a.crec && a.seg_g) hipLaunchKernelGGL((k_index_segs<CPW, NCW, false, true, ND, true>), dim3(sgrid), blk, 0, s, a);
         else if (a.crec) hipLaunchKernelGGL((k_index<CPW, NCW, false, true, ND, true>), dim3(grid), blk, 0, s, a);
+        // (the three-input fold: full records only)
+        else if (a.seg_g && a.fold3) hipLaunchKernelGGL((k_index_segs<CPW, NCW, false, true, ND, false, true>), dim3(sgrid), blk, 0, s, a);
+        else if (a.fold3) hipLaunchKernelGGL((k_index<CPW, NCW, false, true, ND, false, true>), dim3(grid), blk, 0, s, a);
         else if (a.seg_g) hipLaunchKernelGGL((k_index_segs<CPW, NCW, false, true, ND>), dim3(sgrid), blk, 0, s, a);
         else hipLaunchKernelGGL((k_index<CPW, NCW, false, true, ND>), dim3(grid), blk, 0, s, a);
         return hipGetLastError();
