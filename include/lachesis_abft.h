@@ -161,7 +161,16 @@ int lx_abft_reset(lx_abft *a, uint32_t epoch, uint32_t n_validators, const uint3
  *     no epoch and must be re-submitted by the caller (as the reference test
  *     drivers do, abft/event_processing_test.go:145-150).
  * Every claim of the batch is checked before its elections run, so events
- * past a sealing frame carry this epoch's frame or LX_FRAME_BUILD. */
+ * past a sealing frame carry this epoch's frame or LX_FRAME_BUILD; a wrong
+ * claim there only costs work: the events up to the seal are processed again
+ * alone and the call returns as for a seal.
+ * Work on untrusted claims: a batch in which every event claims a frame is
+ * evaluated before any claim is verified, claim - selfParentFrame frame steps
+ * per event.  One pass queues at most 2 n + 4 n_validators + 64 such steps
+ * (or one event's alone, however long its climb); a batch that asks for more
+ * is processed in several passes inside the call, each over verified frames,
+ * with the same results, *consumed and return code.  Inflated claims therefore
+ * cost at most one such budget of discarded steps before LX_ERR_FRAME. */
 int lx_abft_process_batch(lx_abft *a, uint32_t n, const uint32_t *creator_idx, const uint32_t *seq,
                           const uint64_t *parent_off, const uint32_t *parent_idx, const uint32_t *claimed_frame,
                           uint32_t *out_frame, uint32_t *consumed);

@@ -749,6 +749,11 @@ int launch_fc_steps(lx_abft *a, const IndexView &iv, const std::vector<FcStep> &
 // was verified, so the answers are exact there; process() redoes that prefix
 // alone (nothing after it is reported).  A claim above every root frame so far
 // + 1 cannot verify (frame top+1 has no roots): the batch is cut there.
+// Work bound: the queued steps are sum(claim(i) - selfParentFrame(i)), all
+// evaluated before the first claim is checked.  process() hands this function
+// at most 2 n + 4 V + 64 of them per pass (n = events of the call; see
+// claimed_pass_len), or the steps of one event alone, and runs the rest of the
+// batch as further passes, so inflated claims cost one such budget at most.
 int compute_frames_claimed(lx_abft *a, uint64_t base, uint32_t n, const uint32_t *creator, const uint32_t *claimed) {
     PassTimer pt("frames");
     IndexView iv;
@@ -1624,8 +1629,80 @@ int add_events(lx_abft *a, uint32_t n, const uint32_t *creator, const uint32_t *
     return 0;
 }
 
+// Work bound of the claimed path.  compute_frames_claimed queues claim(i) -
+// selfParentFrame(i) frame steps for event i before any claim is verified,
+// and its only guard (claim <= top + 1) moves with the claims themselves: V
+// events claiming top + 1, top + 2, ... queue ~V^2 / 2 steps that the
+// reference refuses after one or two.  One pass therefore takes the longest
+// prefix of the batch whose queued steps stay within
+//     kStepsPerEvent * n + kStepsPerValidator * V + kStepsFloor
+// (n = events of the call), and at least one event: a single long climb, a
+// validator back from an outage, is one candidate per step and is always
+// taken whole.  The events behind the cut go through the next pass of the
+// same call, when every frame below them is a verified one again, so a cut
+// changes no result and is never reported as an error; the steps thrown away
+// by a call that ends in LX_ERR_FRAME are within one budget.  An honest batch
+// queues one step per root slot it adds (~1 per event or less) and is not cut.
+constexpr uint64_t kStepsPerEvent = 2, kStepsPerValidator = 4, kStepsFloor = 64;
+
+// events of [0, n) that one claimed pass takes (see above); base = dense
+// index of event 0, not yet added
+uint32_t claimed_pass_len(const lx_abft *a, uint64_t base, uint32_t n, uint64_t budget, const uint32_t *seq,
+                          const uint64_t *poff, const uint32_t *par, const uint32_t *claimed) {
+    uint64_t steps = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        if (seq[i] <= 1 || poff[i + 1] == poff[i]) continue;   // no self-parent: frame 1, no step
+        const uint32_t sp = par[poff[i]];
+        uint32_t spf;
+        if (sp >= base) {
+            if (sp - base >= i) continue;   // not an event before it: the index refuses the pass
+            spf = claimed[sp - base];
+        } else {
+            spf = a->ev_frame[sp];
+        }
+        if (claimed[i] > spf) steps += claimed[i] - spf;
+        if (steps > budget && i) return i;
+    }
+    return n;
+}
+
+int process_pass(lx_abft *a, uint32_t n, const uint32_t *creator, const uint32_t *seq, const uint64_t *poff,
+                 const uint32_t *par, const uint32_t *claimed, uint32_t *out_frame, uint32_t *consumed);
+
+// A claimed batch in passes of bounded speculative work (claimed_pass_len);
+// every other batch in one.
 int process(lx_abft *a, uint32_t n, const uint32_t *creator, const uint32_t *seq, const uint64_t *poff,
             const uint32_t *par, const uint32_t *claimed, uint32_t *out_frame, uint32_t *consumed) {
+    *consumed = 0;
+    if (!n) return 0;
+    if (!claimed || !a->claimed_batch ||
+        std::any_of(claimed, claimed + n, [](uint32_t c) { return c == LX_FRAME_BUILD; }))
+        return process_pass(a, n, creator, seq, poff, par, claimed, out_frame, consumed);
+    const uint64_t budget = kStepsPerEvent * n + kStepsPerValidator * a->V + kStepsFloor;
+    std::vector<uint64_t> off;
+    for (uint32_t lo = 0; lo < n;) {
+        const uint32_t epoch = a->epoch;
+        const uint32_t m = claimed_pass_len(a, a->ev_frame.size(), n - lo, budget, seq + lo, poff + lo, par, claimed + lo);
+        uint32_t c = 0;
+        int rc;
+        if (lo == 0 && m == n) {
+            rc = process_pass(a, n, creator, seq, poff, par, claimed, out_frame, &c);
+        } else {
+            off.resize(m + 1);   // parent offsets of the pass from 0
+            for (uint32_t i = 0; i <= m; i++) off[i] = poff[lo + i] - poff[lo];
+            rc = process_pass(a, m, creator + lo, seq + lo, off.data(), par + poff[lo], claimed + lo,
+                              out_frame ? out_frame + lo : nullptr, &c);
+        }
+        *consumed += c;
+        // an error, or a seal (the events behind it belong to the next epoch: the caller's)
+        if (rc || c < m || a->epoch != epoch) return rc;
+        lo += m;
+    }
+    return 0;
+}
+
+int process_pass(lx_abft *a, uint32_t n, const uint32_t *creator, const uint32_t *seq, const uint64_t *poff,
+                 const uint32_t *par, const uint32_t *claimed, uint32_t *out_frame, uint32_t *consumed) {
     *consumed = 0;
     if (!n) return 0;
     const uint64_t base = a->ev_frame.size();
@@ -1648,10 +1725,14 @@ int process(lx_abft *a, uint32_t n, const uint32_t *creator, const uint32_t *seq
         int rc = lx_drop_not_flushed(a->ix);
         if (rc) return a->ixfail(rc);
         uint32_t c = 0;
-        if (bad) ARC(process(a, bad, creator, seq, poff, par, claimed, out_frame, &c));
+        const uint32_t epoch = a->epoch;
+        if (bad) ARC(process_pass(a, bad, creator, seq, poff, par, claimed, out_frame, &c));
         *consumed = c;
-        if (c == bad) a->err = "claimed frame mismatched with calculated";
-        return c == bad ? LX_ERR_FRAME : 0;
+        // a seal among the events before it, the last of them included: the
+        // bad event belongs to the next epoch, where its frame was not checked
+        if (c < bad || a->epoch != epoch) return 0;
+        a->err = "claimed frame mismatched with calculated";
+        return LX_ERR_FRAME;
     }
     uint64_t sealed_at;
     std::vector<uint32_t> new_w;
