@@ -467,62 +467,95 @@ BatchArgs batch_args(lx_index *h, uint32_t n, const uint32_t *creator, const uin
     return a;
 }
 
-// The batch walked as h->segments Add-order segments, the partial events'
+// The batch's ordinary walk (the walk plan picks the kernel and the grid,
+// seg_window cuts a segment's window from it)
+IndexArgs index_args(const lx_index *h, uint32_t n, const uint32_t *poff, const uint32_t *par) {
+    IndexArgs ia{};
+    ia.hb = h->hb;
+    ia.la = h->la;
+    ia.stride = h->pstride;
+    ia.cmap = h->sharded() ? h->cmap : nullptr;
+    ia.lap = h->sharded() ? h->lap : nullptr;
+    ia.lap_stride = h->stride;
+    ia.batch_start = (uint32_t)h->n_events;
+    ia.n = n;
+    ia.rec = h->b_rec;
+    ia.crec = h->b_crec_ok ? h->b_crec : nullptr;
+    ia.par_in = par;
+    ia.poff_in = poff;
+    ia.col_list = h->col_list;
+    ia.ncols = h->ncols;
+    ia.branch_first = h->branch_first;
+    ia.brow = h->brow;
+    ia.s_cap = h->s_cap;
+    ia.clk = h->d_clk;
+    return ia;
+}
+
+// LX_PROF=1 in a make WPROF=1 build: the walker's per-wave counters of one
+// batch (IndexArgs::prof), summed up on stderr
+void print_walker_prof(uint32_t n, const std::vector<unsigned long long> &pv) {
+    // summary over workgroups: compute waves (lane sums), loader, drains
+    double sum[kProfWaves * kProfSlots] = {0};
+    uint32_t nb = 0;
+    for (uint32_t b = 0; b < (uint32_t)kProfBlocks; b++) {
+        const unsigned long long *pb = pv.data() + (size_t)b * kProfWaves * kProfSlots;
+        if (!pb[9]) continue;
+        nb++;
+        for (int i = 0; i < kProfWaves * kProfSlots; i++) sum[i] += (double)pb[i];
+    }
+    fprintf(stderr, "[lx_prof] n=%u blocks=%u (means per block)\n", n, nb);
+    {
+        // the slowest workgroups: wall (max over its waves) and the compute waves' no-record passes
+        std::vector<std::pair<double, uint32_t>> wb;
+        for (uint32_t b = 0; b < (uint32_t)kProfBlocks; b++) {
+            const unsigned long long *pb = pv.data() + (size_t)b * kProfWaves * kProfSlots;
+            double wmax = 0;
+            for (int w = 0; w < kProfWaves; w++) wmax = std::max(wmax, (double)pb[w * kProfSlots + 9]);
+            if (wmax > 0) wb.push_back({wmax, b});
+        }
+        std::sort(wb.rbegin(), wb.rend());
+        for (size_t i = 0; i < wb.size() && i < 6; i++) {
+            const unsigned long long *pb = pv.data() + (size_t)wb[i].second * kProfWaves * kProfSlots;
+            double norec = 0;
+            for (int w = 0; w < kProfWaves; w++)
+                if (pb[w * kProfSlots + 10] == 0) norec += (double)pb[w * kProfSlots + 7];
+            fprintf(stderr, "[lx_prof] slow block %u (xcd %u): wall_us=%.0f compute norec=%.0f\n", wb[i].second,
+                    wb[i].second % 8, wb[i].first / 100.0, norec);
+        }
+        if (!wb.empty())
+            fprintf(stderr, "[lx_prof] median block wall_us=%.0f\n", wb[wb.size() / 2].first / 100.0);
+    }
+    for (int w = 0; w < kProfWaves; w++) {
+        const double *q = sum + w * kProfSlots;
+        if (!q[9]) continue;
+        const double role = q[10] / (nb ? nb : 1);
+        if (role > 1.5) {
+            fprintf(stderr, "[lx_prof] wave %d drain: wall_us=%.0f rounds=%.0f spin=%.0f busy_us=%.0f fills=%.0f brc_miss=%.0f\n",
+                    w, q[9] / nb / 100.0, q[3] / nb, q[0] / nb, q[6] / nb / 100.0, q[4] / nb, q[5] / nb);
+        } else if (role > 0.5) {
+            fprintf(stderr, "[lx_prof] wave %d loader: wall_us=%.0f rounds=%.0f iter=%.0f slot_wait=%.0f sleeps=%.0f\n", w,
+                    q[9] / nb / 100.0, q[3] / nb, q[0] / nb, q[1] / nb, q[2] / nb);
+        } else {
+            fprintf(stderr, "[lx_prof] wave %d: wall_us=%.0f wave_passes=%.0f lane: pass=%.0f spin=%.0f chunk=%.0f done=%.0f slow=%.0f fill=%.0f wm=%.0f norec=%.0f  ns/pass=%.1f\n",
+                    w, q[9] / nb / 100.0, q[8] / nb, q[0] / nb, q[1] / nb, q[2] / nb, q[3] / nb, q[4] / nb, q[5] / nb, q[6] / nb,
+                    q[7] / nb, q[9] * 10.0 / (q[8] > 0 ? q[8] : 1));
+            if (q[14] == 0 && q[15] > 0)
+                fprintf(stderr, "[lx_prof] wave %d blocks ahead of the fetched one: landed records %.1f, issued %.1f; behind it: drained %.1f\n",
+                        w, q[11] / q[15], q[12] / q[15], q[13] / q[15]);
+            if (q[14] > 0)
+                fprintf(stderr, "[lx_prof] wave %d cycles/pass: fetch=%.0f (record rt %.0f) fold=%.0f (ring rt %.0f) ovf=%.0f complete=%.0f total=%.0f\n", w,
+                        q[10] / q[8], q[5] / q[8], q[11] / q[8], q[15] / q[8], q[12] / q[8], q[13] / q[8], q[14] / q[8]);
+        }
+    }
+}
+
+// The batch walked as the plan's G Add-order segments, the partial events'
 // rows gathered, LowestAfter filled from the final rows (lx_segment.hip,
 // DESIGN.md section 6b).  `ia` is the batch's ordinary walk; timings into
 // seg_stats.
-// Workgroups of one walk of the batch's columns (launch_index's slice choice,
-// rounded to the 8 XCDs)
-// -- the CUs a walk holds: 12-column slices count only the real slices (the
-// launch's rounding workgroups leave at once and free their CUs for the next
-// walk's: V = 1000, 84 slices, three walks side by side)
-uint32_t walk_grid(const lx_index *h, uint32_t cpw_hint) {
-    const uint32_t nc = h->ncols, cpw = cpw_hint ? cpw_hint : (nc <= 256 ? 1 : nc <= 512 ? 2 : 4);
-    const uint32_t slices = (nc + cpw - 1) / cpw;
-    return cpw == 12 ? slices : (slices + 7) / 8 * 8;
-}
-
-// Segments walked at once on idle compute units: a walk of few columns leaves
-// most CUs idle (C2: 100 columns, 104 workgroups on 256 CUs), and its time is
-// the batch's DAG depth x pass latency, so G concurrent Add-order segments
-// walk ~1/G of the levels each.  Wider slices free more CUs for more
-// segments at a longer pass (relative pass costs of 1-, 2- and 4-column
-// slices as measured on C2: 1, 1.15, 1.28): the slice width with the
-// smallest pass / G wins.  0 when the batch stays one walk; *cpw = the width.
-uint32_t auto_segments(const lx_index *h, uint64_t n, uint32_t *cpw) {
-    if (!h->seg_auto || h->sharded() || h->rowseg() || h->segments > 1 || !h->ncols) return 0;
-    return seg_pick(h, n, cpw);
-}
-
-}  // namespace
-
-// the segment count and slice width auto_segments would pick for n events
-// (row-segment ranks split their own segment by it too, lx_rowseg.cpp)
-uint32_t seg_pick(const lx_index *h, uint64_t n, uint32_t *cpw) {
-    static const float kPass[13] = {0, 1.0f, 1.15f, 0, 1.28f, 0, 0, 0, kPass8, 0, 0, 0, kPass12};
-    // 8- and 12-column slices: packed 16-bit slots only (every seq <= 0xFFFF, no forks)
-    const bool w8 = h->pack16 && h->max_seq <= 0xFFFFu && h->B <= h->V;
-    uint32_t best_g = 0;
-    float best = 1.0f;   // one walk at the default width
-    for (uint32_t c : {1u, 2u, 4u, 8u, 12u}) {
-        if ((h->cpw_hint && c != h->cpw_hint) || (c >= 8 && !w8)) continue;
-        uint32_t G = std::min<uint32_t>(h->n_cus / walk_grid(h, c), kSegLaunchMax);
-        while (G >= 2 && n < (uint64_t)G * kAutoSegEvents) G--;
-        if (G >= 2 && kPass[c] / G < best) {
-            best = kPass[c] / G;
-            best_g = G;
-            *cpw = c;
-        }
-    }
-    return best_g;
-}
-
-uint32_t seg_walk_grid(const lx_index *h, uint32_t cpw) { return walk_grid(h, cpw); }
-
-namespace {
-
-int seg_walk(lx_index *h, IndexArgs ia, const uint32_t *poff, hipStream_t s, uint32_t G, uint32_t cpw) {
-    const uint32_t n = ia.n, bs = ia.batch_start;
+int seg_walk(lx_index *h, IndexArgs ia, const WalkPlan &plan, hipStream_t s) {
+    const uint32_t n = ia.n, bs = ia.batch_start, G = plan.G;
     SegArgs a{};
     a.hb = h->hb;
     a.la = h->la;
@@ -562,40 +595,28 @@ int seg_walk(lx_index *h, IndexArgs ia, const uint32_t *poff, hipStream_t s, uin
     }
     hipEvent_t *ev = h->seg_ev.data();
     HIPCHK(h, lx::launch_seg_tables(a, s));
-    // one launch for all G when they fit the CUs side by side (one workgroup
-    // per CU each: k_index_segs); otherwise one walk after the other
-    ia.cpw_hint = cpw >= 8 && (!ia.pack16 || ia.mask) ? 4 : cpw;
-    cpw = ia.cpw_hint;
-    const bool conc = G <= kSegLaunchMax && G * walk_grid(h, cpw) <= h->n_cus;
+    // one launch for all G when they fit the CUs side by side (k_index_segs),
+    // otherwise one walk after the other
+    const bool conc = plan.one_launch;
     ia.seg = 1;
     ia.ev_branch = h->ev_branch;
     ia.ev_seq = h->ev_seq;
+    ia.seg_j = a.jt;
+    ia.seg_flag = a.pflag;
+    ia.seg_list = a.plist;
+    ia.seg_count = a.pcount;
     if (conc) {
         IndexArgs sk = ia;
         sk.seg_g = G;
         sk.seg_B = a.B;
         for (uint32_t k = 0; k <= G; k++) sk.seg_lo[k] = a.seg_lo[k];
-        sk.seg_j = a.jt;
-        sk.seg_flag = a.pflag;
-        sk.seg_list = a.plist;
-        sk.seg_count = a.pcount;
         HIPCHK(h, hipEventRecord(ev[0], s));
-        HIPCHK(h, lx::launch_index(sk, s));
+        HIPCHK(h, lx::launch_index(sk, plan, s));
         for (uint32_t k = 0; k < G; k++) HIPCHK(h, hipEventRecord(ev[2 * k + 1], s));
     }
     for (uint32_t k = 0; k < G && !conc; k++) {
-        IndexArgs sk = ia;
-        sk.batch_start = a.seg_lo[k];
-        sk.n = a.seg_lo[k + 1] - a.seg_lo[k];
-        sk.rec = ia.rec + (a.seg_lo[k] - bs);
-        sk.crec = ia.crec ? ia.crec + (a.seg_lo[k] - bs) : nullptr;
-        sk.poff_in = poff + (a.seg_lo[k] - bs);
-        sk.seg_j = a.jt + (uint64_t)k * a.B;
-        sk.seg_flag = a.pflag + (a.seg_lo[k] - bs);
-        sk.seg_list = a.plist + (a.seg_lo[k] - bs);
-        sk.seg_count = a.pcount + k;
         HIPCHK(h, hipEventRecord(ev[2 * k], s));
-        HIPCHK(h, lx::launch_index(sk, s));
+        HIPCHK(h, lx::launch_index(seg_window(ia, k, a.seg_lo[k], a.seg_lo[k + 1], a.B), plan, s));
         HIPCHK(h, hipEventRecord(ev[2 * k + 1], s));
     }
     uint32_t pc[kMaxSegments], ec[kMaxSegments];
@@ -676,7 +697,9 @@ int add_batch_dev(lx_index *h, uint32_t n, const uint32_t *creator, const uint32
     a.nofork = (nforks == 0 && B_new == h->V) ? 1u : 0u;
     // compact records for the 8- / 12-column walks: fork-free epoch, every
     // branch and seq within 16 bits (the packed-slot condition)
-    h->b_crec_ok = a.nofork && h->B == h->V && h->pack16 && h->max_seq <= 0xFFFFu && B_new <= 0xFFFFu && h->crec_opt;
+    WalkEpoch we = h->walk_epoch();
+    we.B = B_new;
+    h->b_crec_ok = walk_crec_ok(we, h->crec_opt);
     a.crec = h->b_crec_ok ? h->b_crec : nullptr;
     // pointer jumping along in-batch self-parent chains: a chain has at most
     // min(n, max seq) events, ceil(log2) + 1 rounds resolve it (k_finalize flags
@@ -706,36 +729,13 @@ int add_batch_dev(lx_index *h, uint32_t n, const uint32_t *creator, const uint32
     if (nforks || h->ncols == 0)
         if ((rc = rebuild_columns(h))) return rc;
 
-    IndexArgs ia{};
-    ia.hb = h->hb;
-    ia.la = h->la;
-    ia.stride = h->pstride;
-    ia.cmap = h->sharded() ? h->cmap : nullptr;
-    ia.lap = h->sharded() ? h->lap : nullptr;
-    ia.lap_stride = h->stride;
-    ia.batch_start = (uint32_t)h->n_events;
-    ia.n = n;
-    ia.rec = h->b_rec;
-    ia.crec = h->b_crec_ok ? h->b_crec : nullptr;
-    ia.par_in = par;
-    ia.poff_in = poff;
-    ia.col_list = h->col_list;
-    ia.ncols = h->ncols;
-    ia.branch_first = h->branch_first;
-    ia.brow = h->brow;
-    ia.s_cap = h->s_cap;
-    ia.mask = (h->B > h->V) ? 1u : 0u;
-    ia.cpw_hint = h->cpw_hint;
-    ia.pack16 = h->pack16 && h->max_seq <= 0xFFFFu;
-    ia.fold3 = ia.pack16 && h->fold3 && h->max_seq <= kFold3MaxSeq;
-    ia.seg_xmap = h->seg_xmap_opt ? 1u : 0u;
-    if (ia.cpw_hint >= 8 && (!ia.pack16 || ia.mask)) ia.cpw_hint = 4;   // 8- / 12-column slots: packed, fork-free
     const size_t prof_n = (size_t)kProfBlocks * kProfWaves * kProfSlots;
     if (!h->d_clk) {
         HIPCHK(h, hipMalloc(&h->d_clk, (1 + 3ull * kClkBlocks) * 8));
         HIPCHK(h, hipMemsetAsync(h->d_clk, 0, (1 + 3ull * kClkBlocks) * 8, s));
     }
-    ia.clk = h->d_clk;
+    IndexArgs ia = index_args(h, n, poff, par);
+    const WalkPlan plan = walk_plan(h->walk_epoch(), n);   // (a row-segment rank makes its own, rs_begin)
     if (h->prof) {
         HIPCHK(h, hipMalloc(&ia.prof, prof_n * 8));
         HIPCHK(h, hipMemsetAsync(ia.prof, 0, prof_n * 8, s));
@@ -745,10 +745,10 @@ int add_batch_dev(lx_index *h, uint32_t n, const uint32_t *creator, const uint32
         if ((rc = rs_planes(h, n))) return rc;   // own rows only (+ the virtual bases)
         ia.hb = h->hb;
         ia.la = h->la;
-        if ((rc = rs_begin(h, ia, poff, s))) return rc;
-    } else if (h->segments > 1 && !h->sharded() && n >= 64ull * h->segments) {
-        if ((rc = seg_walk(h, ia, poff, s, h->segments, h->cpw_hint))) return rc;
-    } else if (h->dbl && !ia.mask && !h->sharded() && h->B <= kDblMaxB && n >= 16ull * h->B && n <= 0xFFFFu &&
+        if ((rc = rs_begin(h, ia, s))) return rc;
+    } else if (plan.G && h->segments > 1) {   // option segments
+        if ((rc = seg_walk(h, ia, plan, s))) return rc;
+    } else if (h->dbl && h->B <= h->V && !h->sharded() && h->B <= kDblMaxB && n >= 16ull * h->B && n <= 0xFFFFu &&
                dbl_lds_bytes(n, h->B) <= kDblLds) {
         // few branches, no forks: HB by frontier doubling in one workgroup
         // (the walker's time is levels x pass, and such epochs are deep chains)
@@ -768,10 +768,10 @@ int add_batch_dev(lx_index *h, uint32_t n, const uint32_t *creator, const uint32
         da.brow = h->brow;
         da.s_cap = h->s_cap;
         HIPCHK(h, lx::launch_dbl(da, s));
-    } else if (uint32_t cpw = 0, G = auto_segments(h, n, &cpw); G) {
-        if ((rc = seg_walk(h, ia, poff, s, G, cpw))) return rc;
+    } else if (plan.G) {   // side-by-side segments worth it (walk_seg_pick)
+        if ((rc = seg_walk(h, ia, plan, s))) return rc;
     } else {
-        HIPCHK(h, lx::launch_index(ia, s));
+        HIPCHK(h, lx::launch_index(ia, plan, s));
     }
     HIPCHK(h, hipEventRecord(h->ev[2], s));
     if (h->prof) {
@@ -779,59 +779,7 @@ int add_batch_dev(lx_index *h, uint32_t n, const uint32_t *creator, const uint32
         HIPCHK(h, hipMemcpyAsync(pv.data(), ia.prof, prof_n * 8, hipMemcpyDeviceToHost, s));
         HIPCHK(h, hipStreamSynchronize(s));
         HIPCHK(h, hipFree(ia.prof));
-        // summary over workgroups: compute waves (lane sums), loader, drains
-        double sum[kProfWaves * kProfSlots] = {0};
-        uint32_t nb = 0;
-        for (uint32_t b = 0; b < (uint32_t)kProfBlocks; b++) {
-            const unsigned long long *pb = pv.data() + (size_t)b * kProfWaves * kProfSlots;
-            if (!pb[9]) continue;
-            nb++;
-            for (int i = 0; i < kProfWaves * kProfSlots; i++) sum[i] += (double)pb[i];
-        }
-        fprintf(stderr, "[lx_prof] n=%u blocks=%u (means per block)\n", n, nb);
-        {
-            // the slowest workgroups: wall (max over its waves) and the compute waves' no-record passes
-            std::vector<std::pair<double, uint32_t>> wb;
-            for (uint32_t b = 0; b < (uint32_t)kProfBlocks; b++) {
-                const unsigned long long *pb = pv.data() + (size_t)b * kProfWaves * kProfSlots;
-                double wmax = 0;
-                for (int w = 0; w < kProfWaves; w++) wmax = std::max(wmax, (double)pb[w * kProfSlots + 9]);
-                if (wmax > 0) wb.push_back({wmax, b});
-            }
-            std::sort(wb.rbegin(), wb.rend());
-            for (size_t i = 0; i < wb.size() && i < 6; i++) {
-                const unsigned long long *pb = pv.data() + (size_t)wb[i].second * kProfWaves * kProfSlots;
-                double norec = 0;
-                for (int w = 0; w < kProfWaves; w++)
-                    if (pb[w * kProfSlots + 10] == 0) norec += (double)pb[w * kProfSlots + 7];
-                fprintf(stderr, "[lx_prof] slow block %u (xcd %u): wall_us=%.0f compute norec=%.0f\n", wb[i].second,
-                        wb[i].second % 8, wb[i].first / 100.0, norec);
-            }
-            if (!wb.empty())
-                fprintf(stderr, "[lx_prof] median block wall_us=%.0f\n", wb[wb.size() / 2].first / 100.0);
-        }
-        for (int w = 0; w < kProfWaves; w++) {
-            const double *q = sum + w * kProfSlots;
-            if (!q[9]) continue;
-            const double role = q[10] / (nb ? nb : 1);
-            if (role > 1.5) {
-                fprintf(stderr, "[lx_prof] wave %d drain: wall_us=%.0f rounds=%.0f spin=%.0f busy_us=%.0f fills=%.0f brc_miss=%.0f\n",
-                        w, q[9] / nb / 100.0, q[3] / nb, q[0] / nb, q[6] / nb / 100.0, q[4] / nb, q[5] / nb);
-            } else if (role > 0.5) {
-                fprintf(stderr, "[lx_prof] wave %d loader: wall_us=%.0f rounds=%.0f iter=%.0f slot_wait=%.0f sleeps=%.0f\n", w,
-                        q[9] / nb / 100.0, q[3] / nb, q[0] / nb, q[1] / nb, q[2] / nb);
-            } else {
-                fprintf(stderr, "[lx_prof] wave %d: wall_us=%.0f wave_passes=%.0f lane: pass=%.0f spin=%.0f chunk=%.0f done=%.0f slow=%.0f fill=%.0f wm=%.0f norec=%.0f  ns/pass=%.1f\n",
-                        w, q[9] / nb / 100.0, q[8] / nb, q[0] / nb, q[1] / nb, q[2] / nb, q[3] / nb, q[4] / nb, q[5] / nb, q[6] / nb,
-                        q[7] / nb, q[9] * 10.0 / (q[8] > 0 ? q[8] : 1));
-                if (q[14] == 0 && q[15] > 0)
-                    fprintf(stderr, "[lx_prof] wave %d blocks ahead of the fetched one: landed records %.1f, issued %.1f; behind it: drained %.1f\n",
-                            w, q[11] / q[15], q[12] / q[15], q[13] / q[15]);
-                if (q[14] > 0)
-                    fprintf(stderr, "[lx_prof] wave %d cycles/pass: fetch=%.0f (record rt %.0f) fold=%.0f (ring rt %.0f) ovf=%.0f complete=%.0f total=%.0f\n", w,
-                            q[10] / q[8], q[5] / q[8], q[11] / q[8], q[15] / q[8], q[12] / q[8], q[13] / q[8], q[14] / q[8]);
-            }
-        }
+        print_walker_prof(n, pv);
     }
     if (h->B > h->V && h->n_cheat && !h->rowseg()) {   // a row-segment rank marks its rows at lx_rowseg_finish
         MarkArgs m{};

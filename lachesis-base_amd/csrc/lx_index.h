@@ -323,6 +323,26 @@ struct lx_index {
     uint64_t rs_hslot_cap = 0, rs_rhb_cap = 0, rs_lslot_cap = 0, rs_rla_cap = 0;   // (receive areas: rows x pstride)
     bool rowseg() const { return rs_count >= 1; }   // seg_count = 1: one rank, the whole epoch
 
+    // the epoch and the options as the walk plan sees them (lx_walk_plan.h)
+    WalkEpoch walk_epoch() const {
+        WalkEpoch e{};
+        e.ncols = ncols;
+        e.V = V;
+        e.B = B;
+        e.max_seq = max_seq;
+        e.n_cus = n_cus;
+        e.sharded = sharded();
+        e.rowseg = rowseg();
+        e.crec = b_crec_ok;
+        e.cpw = cpw_hint;
+        e.pack16 = pack16;
+        e.fold3 = fold3;
+        e.seg_xmap = seg_xmap_opt;
+        e.seg_auto = seg_auto;
+        e.segments = segments;
+        return e;
+    }
+
     int fail(int code, const char *fmt, ...) {
         char buf[512];
         va_list ap;
@@ -357,11 +377,9 @@ struct Add1Delta {
 };
 int flush_add1_row(lx_index *h, uint32_t a, uint32_t *evk_dev, uint32_t n_slots, uint8_t *tag_dev, uint8_t *out_dev,
                    uint32_t *psum_dev, const Add1Delta *delta);   // 1: not applicable
-int rs_begin(lx_index *h, IndexArgs ia, const uint32_t *poff, hipStream_t s);   // lx_rowseg.cpp
+int rs_begin(lx_index *h, IndexArgs ia, hipStream_t s);   // lx_rowseg.cpp
 int rs_planes(lx_index *h, uint32_t n);          // lx_rowseg.cpp: own rows of an n-event epoch
 void rs_planes_free(lx_index *h);
-uint32_t seg_pick(const lx_index *h, uint64_t n, uint32_t *cpw);    // lx_capi.cpp (auto_segments)
-uint32_t seg_walk_grid(const lx_index *h, uint32_t cpw);
 void rs_free(lx_index *h);
 void srv_stop(lx_index *h);   // lx_capi.cpp: the resident row server leaves
 void fcc_destroy(lx_index *h);

@@ -23,6 +23,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "lx_walk_plan.h"
+
 #define LX_NONE 0xFFFFFFFFu
 #define LX_MARK 0x80000000u
 #define LX_SEQ_MASK 0x7FFFFFFFu
@@ -60,15 +62,14 @@ constexpr uint32_t kCrecWide = 0xFFFFFFFFu;
 // v_pk_maximum3_f16 on raw seq words: for the bit patterns 0x0000..kFold3MaxSeq
 // (non-negative finite f16, denormals kept: hipcc's default f16 denormal mode)
 // IEEE order is unsigned-integer order, so on words whose halves all lie in
-// that range it computes the same function as two v_pk_max_u16
-constexpr uint32_t kFold3MaxSeq = 0x7BFFu;
+// that range (up to kFold3MaxSeq, lx_walk_plan.h) it computes the same
+// function as two v_pk_max_u16
 __device__ __forceinline__ uint32_t pk_max3_f16(uint32_t a, uint32_t b, uint32_t c) {
     uint32_t d;
     asm("v_pk_maximum3_f16 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
     return d;
 }
 
-constexpr uint32_t kSegLaunchMax = 32;   // segments of one k_index_segs launch
 struct IndexArgs {
     uint32_t *hb;
     uint32_t *la;
@@ -86,17 +87,12 @@ struct IndexArgs {
     const uint32_t *branch_first;
     const uint32_t *brow;
     uint32_t s_cap;
-    uint32_t mask;               // older rows may carry fork marks
-    uint32_t cpw_hint;           // columns per workgroup (0 = auto; lx_set_option "cpw", tests)
     unsigned long long *prof;    // per-wave counters (make WPROF=1 builds only), kProfSlots per wave
     unsigned long long *clk;     // walk clock (lx_last_walk_clock): [0] grid size, then per workgroup
                                  // < kClkBlocks {shader cycles, 100 MHz ticks, XCD} of compute wave 0
     const uint32_t *cmap;        // sharded: global branch -> plane column (NULL = identity)
     uint32_t *lap;               // sharded: LowestAfter rows of own branches (fill target)
     uint64_t lap_stride;         // = global branch capacity
-    uint32_t pack16;             // every seq of the epoch <= 0xFFFF: 16-B packed slots (4-column block walker)
-    uint32_t fold3;              // pack16 and every seq of the epoch <= kFold3MaxSeq: the three-input fold
-                                 // (8- / 12-column packed walks; option fold3 = 0 forces the integer fold)
     // segment walk (lx_segment.hip): parents before batch_start contribute only
     // their own (branch, seq) entry, and no LowestAfter is filled
     uint32_t seg;
@@ -113,13 +109,29 @@ struct IndexArgs {
     uint32_t seg_B;
     uint32_t seg_lo[kSegLaunchMax + 1];
     // 12-column side-by-side walks: workgroup -> (walk << 8 | slice), 0xFFFF
-    // idle, for workgroups < seg_map_n (launch_index fills it when option
-    // seg_xmap is on: every 128-B HB line written by workgroups of one XCD);
-    // seg_map_n = 0: seg_chunk's mapping
-    uint32_t seg_xmap;           // option seg_xmap (lx_set_option)
+    // idle, for workgroups < seg_map_n (WalkPlan::seg_map, option seg_xmap:
+    // every 128-B HB line written by workgroups of one XCD); seg_map_n = 0:
+    // seg_chunk's mapping
     uint32_t seg_map_n;
     uint16_t seg_map[256];
 };
+// Segment k = events [lo, hi) of the batch `b` walks: its window of the
+// batch's records, parent offsets and partial-event flags / list, its J table
+// (B entries per segment) and its partial-event count
+__host__ __device__ inline IndexArgs seg_window(const IndexArgs &b, uint32_t k, uint32_t lo, uint32_t hi, uint32_t B) {
+    IndexArgs a = b;
+    const uint32_t off = lo - b.batch_start;
+    a.batch_start = lo;
+    a.n = hi - lo;
+    a.rec = b.rec + off;
+    a.crec = b.crec ? b.crec + off : nullptr;
+    a.poff_in = b.poff_in + off;
+    a.seg_j = b.seg_j + (uint64_t)k * B;
+    a.seg_flag = b.seg_flag + off;
+    a.seg_list = b.seg_list + off;
+    a.seg_count = b.seg_count + k;
+    return a;
+}
 // k_dbl (lx_dbl.hip): HighestBefore by frontier doubling in one workgroup's
 // LDS, for fork-free batches with few branches
 struct DblArgs {
@@ -625,9 +637,6 @@ struct VoteArgs {
 // each walked with its boundary parents as own entries only (IndexArgs::seg),
 // then fixed up to the reference's rows.
 constexpr uint32_t kMaxSegments = 64;
-constexpr uint64_t kAutoSegEvents = 32768;
-constexpr float kPass12 = 2.1f;  // 12-column slices (C3: three walks 50.0 ms vs two 8-column walks 61.2 ms -> 1.7 x 3 / 2 x 50.0 / 61.2)
-constexpr float kPass8 = 1.7f;   // pass cost of 8- vs 1-column slices (8 compute + 7 drain waves; C3 one walk: 121.7 ms at 8 columns, 91.4 at 4 = 1.28)
 struct SegArgs {
     uint32_t *hb;
     uint32_t *la;
@@ -733,7 +742,7 @@ hipError_t launch_small_inline(const SmallInlineArgs &a, hipStream_t s);
 hipError_t launch_add1_row(const Add1RowArgs &a, hipStream_t s);
 hipError_t scan_tmp_bytes(uint32_t n, size_t *bytes);
 hipError_t launch_undo_claims(const BatchArgs &a, hipStream_t s);
-hipError_t launch_index(const IndexArgs &a, hipStream_t s);
+hipError_t launch_index(const IndexArgs &a, const WalkPlan &p, hipStream_t s);   // p: lx_walk_plan.h
 hipError_t launch_dbl(const DblArgs &a, hipStream_t s);
 hipError_t launch_stage(uint32_t *dst, const uint32_t *src, uint64_t words, hipStream_t s);
 hipError_t launch_marks(const MarkArgs &a, hipStream_t s);

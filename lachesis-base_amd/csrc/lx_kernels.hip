@@ -665,7 +665,7 @@ __device__ __forceinline__ void index_body(const IndexArgs &a, const uint32_t sl
 
     // col = global branch (semantics), pc = plane column (addressing; differs
     // from col only in a column-sharded handle, which stores its own columns).
-    // 12-column slices (whole handles only, launch_index) use the identity
+    // 12-column slices (whole handles only, walk_variant) use the identity
     // column list: col = pc = c0 + k, computed where used, and the first seqs
     // live in LDS -- as per-column arrays they held ~60 SGPRs, which spilled
     // to VGPR lanes and cost a v_readlane at every use
@@ -1555,6 +1555,8 @@ __global__ __launch_bounds__(64 * (NCW + 1 + ND)) void k_index_segs(IndexArgs a0
         k = blockIdx.x / per;
         slice = (w % 8) * a0.slices_per_xcd + w / 8;   // XCD-aware: neighbouring slices share an L2
     }
+    // segment k's window: seg_window() (lx_internal.h) spelled out -- through
+    // the helper the compiler schedules these kernels differently
     IndexArgs a = a0;
     const uint32_t lo = a0.seg_lo[k], off = lo - a0.batch_start;
     a.batch_start = lo;
@@ -1573,98 +1575,47 @@ __global__ __launch_bounds__(64 * (NCW + 1 + ND)) void k_index_segs(IndexArgs a0
     wc.stop(a0.clk, slice < a.n_slices);
 }
 
-template <int CPW, int NCW, int ND = kND>
-static hipError_t launch_index_t(const IndexArgs &a0, hipStream_t s) {
-    IndexArgs a = a0;
-    a.n_slices = (a.ncols + CPW - 1) / CPW;
-    a.slices_per_xcd = (a.n_slices + 7) / 8;
-    const uint32_t grid = a.slices_per_xcd * 8;
+// One walker instance, as one walk or as the plan's segments side by side
+template <int CPW, int NCW, int ND, bool MASKED, bool PK, bool CR, bool F3>
+static void launch_walk(const IndexArgs &a, const WalkPlan &p, hipStream_t s) {
     const dim3 blk(64 * (NCW + 1 + ND));
-    if constexpr (CPW >= 8) {   // packed fork-free epochs only
-        if (!a.pack16 || a.mask) return hipErrorInvalidValue;
-        // (12 columns: at most ceil(seg_g * slices / 8) workgroups per XCD, seg_chunk)
-        uint32_t sgrid = CPW == 12 ? 8 * (a.seg_g * (a.n_slices / 8) + (a.seg_g * (a.n_slices % 8) + 7) / 8)
-                                   : grid * a.seg_g;
-        a.seg_map_n = 0;
-        if (CPW == 12 && a.seg_g && a.seg_xmap && a.n_slices <= 255) {
-            // option seg_xmap: groups of 8 slices (96 columns = three 128-B HB
-            // lines) stay on one XCD, so every HB line is assembled in one L2;
-            // whole groups go round-robin to the least-loaded XCD, the short
-            // last group of each walk after them
-            std::vector<std::vector<uint16_t>> xl(8);
-            auto put = [&](uint32_t k, uint32_t s0, uint32_t cnt) {
-                uint32_t x = 0;
-                for (uint32_t y = 1; y < 8; y++)
-                    if (xl[y].size() < xl[x].size()) x = y;
-                for (uint32_t s = s0; s < s0 + cnt; s++) xl[x].push_back((uint16_t)(k << 8 | s));
-            };
-            for (uint32_t k = 0; k < a.seg_g; k++)
-                for (uint32_t s0 = 0; s0 + 8 <= a.n_slices; s0 += 8) put(k, s0, 8);
-            if (a.n_slices % 8)
-                for (uint32_t k = 0; k < a.seg_g; k++) put(k, a.n_slices / 8 * 8, a.n_slices % 8);
-            size_t mx = 0;
-            for (auto &l : xl) mx = std::max(mx, l.size());
-            if (8 * mx <= 256 && 8 * mx <= sgrid + 8) {
-                a.seg_map_n = (uint32_t)(8 * mx);
-                for (uint32_t g = 0; g < a.seg_map_n; g++)
-                    a.seg_map[g] = g / 8 < xl[g % 8].size() ? xl[g % 8][g / 8] : (uint16_t)0xFFFFu;
-                sgrid = a.seg_map_n;
-            }
-        }
-        // compact records when the batch wrote them (fork-free, 16-bit branches and seqs)
-        if (a.crec && a.seg_g) hipLaunchKernelGGL((k_index_segs<CPW, NCW, false, true, ND, true>), dim3(sgrid), blk, 0, s, a);
-        else if (a.crec) hipLaunchKernelGGL((k_index<CPW, NCW, false, true, ND, true>), dim3(grid), blk, 0, s, a);
-        // (the three-input fold: full records only)
-        else if (a.seg_g && a.fold3) hipLaunchKernelGGL((k_index_segs<CPW, NCW, false, true, ND, false, true>), dim3(sgrid), blk, 0, s, a);
-        else if (a.fold3) hipLaunchKernelGGL((k_index<CPW, NCW, false, true, ND, false, true>), dim3(grid), blk, 0, s, a);
-        else if (a.seg_g) hipLaunchKernelGGL((k_index_segs<CPW, NCW, false, true, ND>), dim3(sgrid), blk, 0, s, a);
-        else hipLaunchKernelGGL((k_index<CPW, NCW, false, true, ND>), dim3(grid), blk, 0, s, a);
-        return hipGetLastError();
-    } else {
-    if (a.seg_g) {   // segments side by side (walk_grid-sized blocks of workgroups)
-        const dim3 g(grid * a.seg_g);
-        if constexpr (CPW == 4) {
-            if (a.pack16) {
-                if (a.mask) hipLaunchKernelGGL((k_index_segs<CPW, NCW, true, true>), g, blk, 0, s, a);
-                else hipLaunchKernelGGL((k_index_segs<CPW, NCW, false, true>), g, blk, 0, s, a);
-                return hipGetLastError();
-            }
-        }
-        if (a.mask) hipLaunchKernelGGL((k_index_segs<CPW, NCW, true, false>), g, blk, 0, s, a);
-        else hipLaunchKernelGGL((k_index_segs<CPW, NCW, false, false>), g, blk, 0, s, a);
-        return hipGetLastError();
-    }
-    if constexpr (CPW == 4) {
-        if (a.pack16) {   // every seq of the epoch fits 16 bits: one 16-B slot unit
-            if (a.mask) hipLaunchKernelGGL((k_index<CPW, NCW, true, true>), dim3(grid), blk, 0, s, a);
-            else hipLaunchKernelGGL((k_index<CPW, NCW, false, true>), dim3(grid), blk, 0, s, a);
-            return hipGetLastError();
-        }
-    }
-    if (a.mask) hipLaunchKernelGGL((k_index<CPW, NCW, true, false>), dim3(grid), blk, 0, s, a);
-    else hipLaunchKernelGGL((k_index<CPW, NCW, false, false>), dim3(grid), blk, 0, s, a);
-    return hipGetLastError();
-    }
+    if (p.one_launch) hipLaunchKernelGGL((k_index_segs<CPW, NCW, MASKED, PK, ND, CR, F3>), dim3(p.seg_grid), blk, 0, s, a);
+    else hipLaunchKernelGGL((k_index<CPW, NCW, MASKED, PK, ND, CR, F3>), dim3(p.grid), blk, 0, s, a);
 }
 
-hipError_t launch_index(const IndexArgs &a, hipStream_t s) {
-    if (a.n == 0 || a.ncols == 0) return hipSuccess;
-    if (a.stride * 4 > 0xFFFFFFFFull) return hipErrorInvalidValue;   // the drains' 32-bit row pitch
-    // columns per workgroup: the fewest that still leave at most ~256
-    // workgroups (one per CU); the pass gets shorter with fewer columns per
-    // slice, and the walk time is levels x pass latency whatever the number of
-    // workgroups.  Compute waves: 8 on 1- / 2-column slices (11 slowed C2 by
-    // 7 %), 11 on 4-column slices (16 waves with the loader and 4 drains, the
-    // workgroup limit: C3 walk -1.8 % against 8).
-    const uint32_t cpw = a.cpw_hint ? a.cpw_hint : (a.ncols <= 256 ? 1 : a.ncols <= 512 ? 2 : 4);
-    if (cpw <= 1) return launch_index_t<1, 8>(a, s);
-    if (cpw <= 2) return launch_index_t<2, 8>(a, s);
-    // 8 columns: twice the drains' work per event (HB row, range fills), so
-    // 7 drain waves beside 8 compute waves
-    if (cpw == 8) return launch_index_t<8, 8, 7>(a, s);
-    // 12 columns (V = 1000: 84 slices, three walks side by side on 256 CUs)
-    if (cpw == 12) return a.cmap ? launch_index_t<8, 8, 7>(a, s) : launch_index_t<12, 8, 7>(a, s);
-    return launch_index_t<4, 11>(a, s);
+// The walker's instances: columns per workgroup, compute waves, drain waves,
+// masked, packed slots, compact records, three-input fold -- the variants
+// walk_variant() (lx_walk_plan.h) resolves to, each as k_index and k_index_segs
+#define LX_WALK_VARIANTS(X)                                                              \
+    X(1, 8, kND, false, false, false, false) X(1, 8, kND, true, false, false, false)     \
+    X(2, 8, kND, false, false, false, false) X(2, 8, kND, true, false, false, false)     \
+    X(4, 11, kND, false, false, false, false) X(4, 11, kND, true, false, false, false)   \
+    X(4, 11, kND, false, true, false, false) X(4, 11, kND, true, true, false, false)     \
+    X(8, 8, 7, false, true, false, false) X(8, 8, 7, false, true, true, false)           \
+    X(8, 8, 7, false, true, false, true)                                                 \
+    X(12, 8, 7, false, true, false, false) X(12, 8, 7, false, true, true, false)         \
+    X(12, 8, 7, false, true, false, true)
+constexpr uint32_t walk_key(uint32_t cpw, uint32_t ncw, uint32_t nd, bool masked, bool packed, bool crec, bool fold3) {
+    return cpw | ncw << 4 | nd << 8 | masked << 12 | packed << 13 | crec << 14 | fold3 << 15;
+}
+
+// The walk the plan describes (lx_walk_plan.h decides, nothing is decided here)
+hipError_t launch_index(const IndexArgs &a0, const WalkPlan &p, hipStream_t s) {
+    if (a0.n == 0 || a0.ncols == 0) return hipSuccess;
+    if (a0.stride * 4 > 0xFFFFFFFFull) return hipErrorInvalidValue;   // the drains' 32-bit row pitch
+    IndexArgs a = a0;
+    a.n_slices = p.n_slices;
+    a.slices_per_xcd = p.slices_per_xcd;
+    a.seg_map_n = p.seg_map_n;
+    for (uint32_t g = 0; g < p.seg_map_n; g++) a.seg_map[g] = p.seg_map[g];
+    switch (walk_key(p.cpw, p.ncw, p.nd, p.masked, p.packed, p.crec, p.fold3)) {
+#define X(CPW, NCW, ND, M, PK, CR, F3) \
+    case walk_key(CPW, NCW, ND, M, PK, CR, F3): launch_walk<CPW, NCW, ND, M, PK, CR, F3>(a, p, s); break;
+        LX_WALK_VARIANTS(X)
+#undef X
+    default: return hipErrorInvalidValue;   // no instance: not a plan of walk_variant()
+    }
+    return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------- fork marks

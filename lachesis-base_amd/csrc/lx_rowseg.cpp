@@ -204,15 +204,16 @@ void rs_free(lx_index *h) {
 // lx_add_batch on a row-segment rank (the epoch's only batch, assigned): walk
 // the own segment, list the rows its partial events and its LowestAfter pass
 // need from the other ranks
-int rs_begin(lx_index *h, IndexArgs ia, const uint32_t *poff, hipStream_t s) {
+int rs_begin(lx_index *h, IndexArgs ia, hipStream_t s) {
     const uint32_t G = h->rs_count, k = h->rs_rank, n = ia.n;
-    // sub-segments per rank: the segment count auto_segments would pick for a
+    const WalkEpoch we = h->walk_epoch();
+    // sub-segments per rank: the segment count walk_seg_pick finds for a
     // rank's share of the epoch (the same on every rank: it depends only on
     // the epoch and the device), or option seg_sub; each >= 64 events
-    uint32_t S = h->rs_sub_opt, cpw = ia.cpw_hint;
+    uint32_t S = h->rs_sub_opt, cpw = we.cpw;
     if (!S) {
         uint32_t c = 0;
-        S = seg_pick(h, (uint64_t)n / G, &c);
+        S = walk_seg_pick(we, (uint64_t)n / G, &c);
         if (S >= 2) cpw = c;
         else S = 1;
     }
@@ -260,33 +261,25 @@ int rs_begin(lx_index *h, IndexArgs ia, const uint32_t *poff, hipStream_t s) {
     ia.seg = 1;
     ia.ev_branch = h->ev_branch;
     ia.ev_seq = h->ev_seq;
-    const IndexArgs ib = ia;   // the batch's walk arguments (records from event 0)
+    ia.seg_j = a.jt;
+    ia.seg_flag = a.pflag;
+    ia.seg_list = a.plist;
+    ia.seg_count = a.pcount;
     const uint32_t k0 = a.own_seg;
     // the own sub-segments: one k_index_segs launch side by side when they fit
-    // the CUs (as a single-GPU batch), else one walk each
-    if (S > 1) ia.cpw_hint = cpw >= 8 && (!ia.pack16 || ia.mask) ? 4 : cpw;
-    const bool conc = S > 1 && S * seg_walk_grid(h, ia.cpw_hint) <= h->n_cus;
+    // the CUs (as a single-GPU batch), else one walk each; the
+    // sub-segments' slice width only when there are any
+    const WalkPlan plan = walk_layout(we, S > 1 ? cpw : we.cpw, S);
     HIPCHK(h, hipEventRecord(h->seg_ev[0], s));
-    for (uint32_t t = 0; t < S; t++) {
-        if (conc && t) break;
-        IndexArgs sk = ia;
-        const uint32_t b0 = h->rs_seg_lo[k0 + t];
-        sk.batch_start = conc ? h->rs_lo : b0;
-        sk.n = conc ? h->rs_hi - h->rs_lo : h->rs_seg_lo[k0 + t + 1] - b0;
-        sk.rec = ib.rec + sk.batch_start;
-        sk.crec = ib.crec ? ib.crec + sk.batch_start : nullptr;
-        sk.poff_in = poff + sk.batch_start;
-        sk.seg_j = a.jt + (uint64_t)(k0 + t) * a.B;
-        sk.seg_flag = a.pflag + sk.batch_start;
-        sk.seg_list = a.plist + sk.batch_start;
-        sk.seg_count = a.pcount + k0 + t;
-        if (conc) {
-            sk.seg_g = S;
-            sk.seg_B = a.B;
-            for (uint32_t u = 0; u <= S; u++) sk.seg_lo[u] = h->rs_seg_lo[k0 + u];
-        }
-        HIPCHK(h, lx::launch_index(sk, s));
+    if (plan.one_launch) {
+        IndexArgs sk = seg_window(ia, k0, h->rs_lo, h->rs_hi, a.B);
+        sk.seg_g = S;
+        sk.seg_B = a.B;
+        for (uint32_t u = 0; u <= S; u++) sk.seg_lo[u] = h->rs_seg_lo[k0 + u];
+        HIPCHK(h, lx::launch_index(sk, plan, s));
     }
+    for (uint32_t t = 0; t < S && !plan.one_launch; t++)
+        HIPCHK(h, lx::launch_index(seg_window(ia, k0 + t, h->rs_seg_lo[k0 + t], h->rs_seg_lo[k0 + t + 1], a.B), plan, s));
     HIPCHK(h, hipEventRecord(h->seg_ev[1], s));
     HIPCHK(h, hipMemcpyAsync(h->rs_npart, a.pcount + k0, 4ull * S, hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipStreamSynchronize(s));
@@ -315,7 +308,7 @@ int rs_begin(lx_index *h, IndexArgs ia, const uint32_t *poff, hipStream_t s) {
     st.segments = G;
     for (uint32_t q = 0; q <= G; q++) st.first_event[q] = h->rs_seg_lo[q * S];
     st.partial[k] = h->rs_npartial;
-    st.one_launch = conc ? 1u : 0u;
+    st.one_launch = plan.one_launch ? 1u : 0u;
     HIPCHK(h, hipEventElapsedTime(&st.walk_ms[k], h->seg_ev[0], h->seg_ev[1]));
     h->rs_state = 1;
     if (!nreq) return rs_fix_partials(h);

@@ -1,8 +1,8 @@
 """Walk time of the headline config (C3: V = 1000, Zipf stakes, 10M events,
 one batch, default options = three side-by-side segments of 12-column slices)
 with whichever library LX_LIB names: median of 5 index steps (ms_index and
-the segment walk from lx_last_segment_stats).  scripts/probes/walk_ab.sh runs
-it alternately on the shipped build and an A/B baseline build."""
+the segment walk from lx_last_segment_stats).  For an A/B, run it alternately
+with LX_LIB on the shipped build and on a build of the commit to compare with."""
 import json
 import os
 import sys
