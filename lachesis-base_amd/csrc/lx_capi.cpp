@@ -50,130 +50,73 @@ static std::atomic<int> g_live_handles{0};
 
 namespace {
 
-void free_wb(lx_index *h) {
-    void *p[] = {h->wb_flag, h->wb_pos, h->wb_la_rows, h->wb_hb_rows, h->wb_buf, h->wb_len, h->wb_la_off,
-                 h->wb_hb_off, h->wb_tmp};
-    for (void *x : p)
-        if (x) (void)hipFree(x);
-    h->wb_flag = h->wb_pos = h->wb_la_rows = h->wb_hb_rows = h->wb_buf = nullptr;
-    h->wb_len = h->wb_la_off = h->wb_hb_off = nullptr;
-    h->wb_tmp = nullptr;
-    h->wb_cap = h->wb_buf_cap = 0;
-    h->wb_tmp_bytes = 0;
-    h->wb_ready = false;
-}
-
+// a re-layout: every buffer of the old layout goes, with the state that describes them
 void free_all(lx_index *h) {
-    free_wb(h);
-    rs_planes_free(h);   // a row-segment rank's hb / la are virtual bases into its own allocations
-    void *ptrs[] = {h->hb, h->la, h->ev_creator, h->ev_seq, h->ev_branch, h->ev_bbefore, h->ev_sp,
-                    h->first_child, h->first_root, h->branch_first, h->branch_creator, h->branch_len, h->brow,
-                    h->wpad, h->col_list, h->cheat_off, h->cheat_br, h->cheat_creator, h->b_creator, h->b_seq,
-                    h->b_poff, h->b_par, h->b_isfork, h->b_rank, h->b_tmpbr, h->b_jmp, h->b_rec, h->scan_tmp,
-                    h->q_a, h->q_b, h->q_out, h->b_crec};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    void *tptrs[] = {h->tail_zw, h->tail_lo, h->tail_cmin, h->wire_flag};
-    for (void *p : tptrs)
-        if (p) (void)hipFree(p);
-    h->tail_zw = h->tail_lo = h->tail_cmin = h->wire_flag = nullptr;
-    h->tail_cap = 0;
-    void *lptrs[] = {h->cheat_brl, h->cheat_crl, h->cmap, h->lap, h->wloc, h->cheat_of, h->fk_w, h->fk_c, h->fk_wch};
-    for (void *p : lptrs)
-        if (p) (void)hipFree(p);
-    h->cheat_brl = h->cheat_crl = h->cmap = h->lap = h->wloc = nullptr;
-    void *gptrs[] = {h->seg_jt, h->seg_cnt, h->seg_mf, h->seg_plist, h->seg_elist};
-    for (void *p : gptrs)
-        if (p) (void)hipFree(p);
-    h->seg_jt = h->seg_cnt = h->seg_mf = h->seg_plist = h->seg_elist = nullptr;
-    h->seg_jt_cap = h->seg_cnt_cap = h->seg_mf_cap = h->seg_plist_cap = h->seg_elist_cap = 0;
-    rs_free(h);
-    h->fk_w = h->fk_c = h->fk_wch = nullptr;
-    h->fk_cap = 0;
+    if (h->rowseg() && h->lay.hb_mem) (void)hipStreamSynchronize(h->stream);   // the walk may still write its rows
+    h->lay = Layout{};
+    h->wb_ready = false;
     h->fk_hi4 = 0;
-    h->cheat_of = nullptr;
-    h->cheat_of_cap = 0;
-    h->cmap_cap = 0;
-    for (uint32_t *p : h->sc_rows)
-        if (p) (void)hipFree(p);
-    void *sptrs[] = {h->sc_flag, h->sc_pos, h->sc_cols, h->sc_tmp};
-    for (void *p : sptrs)
-        if (p) (void)hipFree(p);
-    h->sc_rows.clear();
-    h->sc_nrows.clear();
-    h->sc_flag = h->sc_pos = h->sc_cols = nullptr;
-    h->sc_tmp = nullptr;
-    h->sc_cap = 0;
-    h->sc_tmp_bytes = 0;
     h->sc_events = ~0ull;
     h->sc_cols_B = 0;
-    for (void *p : {(void *)h->sx_len, (void *)h->sx_dmin, (void *)h->sx_rows, (void *)h->sx_meta})
-        if (p) (void)hipFree(p);
-    h->sx_len = h->sx_dmin = h->sx_rows = h->sx_meta = nullptr;
-    h->sx_cap = 0;
-    h->sx_rows_cap = h->sx_meta_cap = 0;
     h->sx_full = true;
     h->sx_active = false;
-    h->hb = h->la = nullptr;
-    h->ev_creator = h->ev_seq = h->ev_branch = h->ev_bbefore = h->ev_sp = h->first_child = nullptr;
-    h->first_root = h->branch_first = h->branch_creator = h->branch_len = h->brow = h->wpad = h->col_list = nullptr;
-    h->cheat_off = h->cheat_br = h->cheat_creator = nullptr;
-    h->b_creator = h->b_seq = h->b_poff = h->b_par = h->b_isfork = h->b_rank = h->b_tmpbr = h->b_jmp = nullptr;
-    h->b_rec = nullptr;
-    h->b_crec = nullptr;
-    h->scan_tmp = nullptr;
-    h->q_a = h->q_b = nullptr;
-    h->q_out = nullptr;
+    h->rs_gen = 0;
+    h->rs_state = 0;
     h->n_cap = h->stride = h->pstride = h->s_cap = 0;
-    h->batch_cap = h->par_cap = h->q_cap = h->cheat_cap = 0;
-    h->scan_bytes = 0;
 }
 
 // a shard's produced LowestAfter rows lap[(col * s_cap + s) * stride + j] in a
 // new shape (local columns, seq capacity, branch capacity), contents kept
 int relayout_lap(lx_index *h, uint32_t ncol, uint32_t nscap, uint32_t nstride) {
-    uint32_t *n = nullptr;
+    DU32 n;
     const uint64_t words = (uint64_t)ncol * nscap * nstride;
-    HIPCHK(h, dalloc(&n, words));
+    HIPCHK(h, n.renew(words));
     HIPCHK(h, hipMemsetAsync(n, 0, words * 4, h->stream));
-    if (h->lap) {
+    if (h->lay.lap) {
         const uint32_t oc = std::min(h->pstride, ncol), os = std::min(h->s_cap, nscap);
         for (uint32_t k = 0; k < oc && os; k++)
             HIPCHK(h, lx::launch_copy_rows(n + (uint64_t)k * nscap * nstride, nstride,
-                                           h->lap + (uint64_t)k * h->s_cap * h->stride, h->stride, os,
+                                           h->lay.lap + (uint64_t)k * h->s_cap * h->stride, h->stride, os,
                                            std::min(h->stride, nstride), h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        (void)hipFree(h->lap);
     }
-    h->lap = n;
+    h->lay.lap = std::move(n);
+    return 0;
+}
+
+// the ordinary planes in a new row pitch: `rows` rows of `ocols` columns kept
+// (none when there is no old plane), the rest zero
+int repitch_planes(lx_index *h, uint32_t npitch, uint64_t rows, uint32_t ocols) {
+    Layout &l = h->lay;
+    for (DU32 *p : {&l.hb_mem, &l.la_mem}) {
+        DU32 n;
+        HIPCHK(h, n.renew(h->n_cap * npitch));
+        HIPCHK(h, hipMemsetAsync(n, 0, h->n_cap * npitch * 4, h->stream));
+        if (*p) HIPCHK(h, lx::launch_copy_rows(n, npitch, *p, ocols, rows, ocols, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        *p = std::move(n);
+    }
+    l.hb = l.hb_mem;
+    l.la = l.la_mem;
     return 0;
 }
 
 // per-event arrays + planes for n_cap events (copies the first `keep` events)
 int grow_events(lx_index *h, uint64_t need) {
     if (need <= h->n_cap) return 0;
+    Layout &l = h->lay;
     uint64_t cap = std::max<uint64_t>({need, h->n_cap + h->n_cap / 2, 4096});
     uint64_t keep = h->hwm;
-    uint32_t **arrs[] = {&h->ev_creator, &h->ev_seq, &h->ev_branch, &h->ev_bbefore, &h->ev_sp, &h->first_child};
-    for (uint32_t **a : arrs) {
-        uint32_t *n = nullptr;
-        HIPCHK(h, dalloc(&n, cap));
-        if (*a && keep) HIPCHK(h, hipMemcpyAsync(n, *a, keep * 4, hipMemcpyDeviceToDevice, h->stream));
-        if (*a) { HIPCHK(h, hipStreamSynchronize(h->stream)); (void)hipFree(*a); }
-        *a = n;
-    }
-    HIPCHK(h, lx::launch_fill_u32(h->first_child + keep, cap - keep, LX_NONE, h->stream));
+    for (DU32 *a : {&l.ev_creator, &l.ev_seq, &l.ev_branch, &l.ev_bbefore, &l.ev_sp, &l.first_child})
+        HIPCHK(h, a->regrow(cap, keep, Fill::none, h->stream));
+    HIPCHK(h, lx::launch_fill_u32(l.first_child + keep, cap - keep, LX_NONE, h->stream));
     // (a row-segment rank allocates the planes of its own rows when it takes
     // its batch: rs_planes)
-    uint32_t **planes[] = {&h->hb, &h->la};
-    for (uint32_t **p : planes) {
-        if (h->rowseg()) break;
-        uint32_t *n = nullptr;
-        HIPCHK(h, dalloc(&n, cap * h->pstride));
-        HIPCHK(h, hipMemsetAsync(n, 0, cap * h->pstride * 4, h->stream));
-        if (*p && keep) HIPCHK(h, hipMemcpyAsync(n, *p, keep * h->pstride * 4, hipMemcpyDeviceToDevice, h->stream));
-        if (*p) { HIPCHK(h, hipStreamSynchronize(h->stream)); (void)hipFree(*p); }
-        *p = n;
+    if (!h->rowseg()) {
+        for (DU32 *p : {&l.hb_mem, &l.la_mem})
+            HIPCHK(h, p->regrow(cap * h->pstride, keep * h->pstride, Fill::all, h->stream));
+        l.hb = l.hb_mem;
+        l.la = l.la_mem;
     }
     h->n_cap = cap;
     return 0;
@@ -182,18 +125,13 @@ int grow_events(lx_index *h, uint64_t need) {
 // LowestAfter tail state sized to the branch capacity; a new table starts at
 // zw = 0 (the next pass re-zeroes every unobserved tail: always correct)
 int ensure_tail(lx_index *h) {
-    if (h->tail_cap >= h->stride && h->tail_zw) return 0;
-    void *tptrs[] = {h->tail_zw, h->tail_lo, h->tail_cmin};
-    if (h->tail_zw) HIPCHK(h, hipStreamSynchronize(h->stream));
-    for (void *p : tptrs)
-        if (p) (void)hipFree(p);
-    h->tail_zw = h->tail_lo = h->tail_cmin = nullptr;
+    Layout &l = h->lay;
+    if (l.tail_cap() >= h->stride && l.tail_zw) return 0;
     const uint64_t t = h->stride;
-    HIPCHK(h, dalloc(&h->tail_zw, t * t));
-    HIPCHK(h, dalloc(&h->tail_lo, t * t));
-    HIPCHK(h, dalloc(&h->tail_cmin, t));
-    HIPCHK(h, hipMemsetAsync(h->tail_zw, 0, t * t * 4, h->stream));
-    h->tail_cap = h->stride;
+    HIPCHK(h, l.tail_zw.renew(t * t, h->stream, true));
+    HIPCHK(h, l.tail_lo.renew(t * t));
+    HIPCHK(h, l.tail_cmin.renew(t));
+    HIPCHK(h, hipMemsetAsync(l.tail_zw, 0, t * t * 4, h->stream));
     return 0;
 }
 
@@ -201,18 +139,18 @@ int la_tail(lx_index *h, hipStream_t s) {
     int rc;
     if ((rc = ensure_tail(h))) return rc;
     TailArgs t{};
-    t.la = h->la;
-    t.hb = h->hb;
+    t.la = h->lay.la;
+    t.hb = h->lay.hb;
     t.stride = h->pstride;
-    t.brow = h->brow;
+    t.brow = h->lay.brow;
     t.s_cap = h->s_cap;
-    t.branch_first = h->branch_first;
-    t.branch_len = h->branch_len;
+    t.branch_first = h->lay.branch_first;
+    t.branch_len = h->lay.branch_len;
     t.B = h->B;
-    t.zw = h->tail_zw;
-    t.lo = h->tail_lo;
-    t.cmin = h->tail_cmin;
-    t.tcap = h->tail_cap;
+    t.zw = h->lay.tail_zw;
+    t.lo = h->lay.tail_lo;
+    t.cmin = h->lay.tail_cmin;
+    t.tcap = h->lay.tail_cap();
     HIPCHK(h, lx::launch_la_tail(t, s));
     h->tail_dirty = true;
     return 0;
@@ -221,50 +159,27 @@ int la_tail(lx_index *h, hipStream_t s) {
 // branch capacity (= plane stride) and per-branch arrays
 int grow_branches(lx_index *h, uint32_t need) {
     if (need <= h->stride) return 0;
+    Layout &l = h->lay;
     uint32_t ns = round_up(std::max<uint32_t>(need, h->stride + h->stride / 4), 64);
     uint32_t os = h->stride;
-    uint64_t keep = h->hwm;
+    int rc;
     if (h->sharded()) {
         // planes hold local columns; the produced LowestAfter rows are B wide
-        int rc;
-        if (h->lap && (rc = relayout_lap(h, h->pstride, h->s_cap, ns))) return rc;
-        uint32_t *nc = nullptr;
-        HIPCHK(h, dalloc(&nc, ns));
+        if (l.lap && (rc = relayout_lap(h, h->pstride, h->s_cap, ns))) return rc;
+        DU32 nc;   // (filled with LX_NONE, not zeros: spelled out)
+        HIPCHK(h, nc.renew(ns));
         HIPCHK(h, lx::launch_fill_u32(nc, ns, LX_NONE, h->stream));
-        if (h->cmap) HIPCHK(h, hipMemcpyAsync(nc, h->cmap, (uint64_t)std::min(os, h->cmap_cap) * 4, hipMemcpyDeviceToDevice, h->stream));
+        if (l.cmap)
+            HIPCHK(h, hipMemcpyAsync(nc, l.cmap, std::min<uint64_t>(os, l.cmap.cap()) * 4, hipMemcpyDeviceToDevice,
+                                     h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        if (h->cmap) (void)hipFree(h->cmap);
-        h->cmap = nc;
-        h->cmap_cap = ns;
-    } else if (h->hb && !h->rowseg()) {   // (row-segment planes: rs_planes, at the batch)
-        uint32_t **planes[] = {&h->hb, &h->la};
-        for (uint32_t **p : planes) {
-            uint32_t *n = nullptr;
-            HIPCHK(h, dalloc(&n, h->n_cap * ns));
-            HIPCHK(h, hipMemsetAsync(n, 0, h->n_cap * ns * 4, h->stream));
-            HIPCHK(h, lx::launch_copy_rows(n, ns, *p, os, keep, os, h->stream));
-            HIPCHK(h, hipStreamSynchronize(h->stream));
-            (void)hipFree(*p);
-            *p = n;
-        }
+        l.cmap = std::move(nc);
+    } else if (l.hb && !h->rowseg()) {   // (row-segment planes: rs_planes, at the batch)
+        if ((rc = repitch_planes(h, ns, h->hwm, os))) return rc;
     }
-    uint32_t **arrs[] = {&h->branch_first, &h->branch_creator, &h->branch_len, &h->wpad, &h->col_list};
-    for (uint32_t **a : arrs) {
-        uint32_t *n = nullptr;
-        HIPCHK(h, dalloc(&n, ns));
-        HIPCHK(h, hipMemsetAsync(n, 0, (uint64_t)ns * 4, h->stream));
-        if (*a) HIPCHK(h, hipMemcpyAsync(n, *a, (uint64_t)os * 4, hipMemcpyDeviceToDevice, h->stream));
-        if (*a) { HIPCHK(h, hipStreamSynchronize(h->stream)); (void)hipFree(*a); }
-        *a = n;
-    }
-    uint32_t *nb = nullptr;
-    HIPCHK(h, dalloc(&nb, (uint64_t)ns * h->s_cap));
-    if (h->brow) {
-        HIPCHK(h, hipMemcpyAsync(nb, h->brow, (uint64_t)os * h->s_cap * 4, hipMemcpyDeviceToDevice, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        (void)hipFree(h->brow);
-    }
-    h->brow = nb;
+    for (DU32 *a : {&l.branch_first, &l.branch_creator, &l.branch_len, &l.wpad, &l.col_list})
+        HIPCHK(h, a->regrow(ns, os, Fill::all, h->stream));
+    HIPCHK(h, l.brow.regrow((uint64_t)ns * h->s_cap, (uint64_t)os * h->s_cap, Fill::none, h->stream));
     h->stride = ns;
     if (!h->sharded()) h->pstride = ns;
     return 0;
@@ -273,14 +188,13 @@ int grow_branches(lx_index *h, uint32_t need) {
 int grow_scap(lx_index *h, uint32_t need) {
     if (need <= h->s_cap) return 0;
     uint32_t ns = std::max<uint32_t>({need, h->s_cap + h->s_cap / 2, 256});
-    uint32_t *nb = nullptr;
-    HIPCHK(h, dalloc(&nb, (uint64_t)h->stride * ns));
-    if (h->brow && h->s_cap) {
-        HIPCHK(h, lx::launch_copy_rows(nb, ns, h->brow, h->s_cap, h->stride, h->s_cap, h->stream));
+    DU32 nb;
+    HIPCHK(h, nb.renew((uint64_t)h->stride * ns));
+    if (h->lay.brow && h->s_cap) {
+        HIPCHK(h, lx::launch_copy_rows(nb, ns, h->lay.brow, h->s_cap, h->stride, h->s_cap, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        (void)hipFree(h->brow);
     }
-    h->brow = nb;
+    h->lay.brow = std::move(nb);
     if (h->sharded()) {
         int rc;
         if ((rc = relayout_lap(h, h->pstride, ns, h->stride))) return rc;
@@ -295,54 +209,27 @@ int grow_local(lx_index *h, uint32_t need) {
     uint32_t np = round_up(std::max<uint32_t>(need, h->pstride + h->pstride / 4), 16);
     int rc;
     if ((rc = relayout_lap(h, np, h->s_cap, h->stride))) return rc;
-    uint32_t **planes[] = {&h->hb, &h->la};
-    for (uint32_t **p : planes) {
-        uint32_t *n = nullptr;
-        HIPCHK(h, dalloc(&n, h->n_cap * np));
-        HIPCHK(h, hipMemsetAsync(n, 0, h->n_cap * np * 4, h->stream));
-        if (*p) HIPCHK(h, lx::launch_copy_rows(n, np, *p, h->pstride, h->hwm, h->pstride, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        if (*p) (void)hipFree(*p);
-        *p = n;
-    }
-    uint32_t *nw = nullptr;
-    HIPCHK(h, dalloc(&nw, np));
-    HIPCHK(h, hipMemsetAsync(nw, 0, np * 4ull, h->stream));
-    if (h->wloc) HIPCHK(h, hipMemcpyAsync(nw, h->wloc, h->pstride * 4ull, hipMemcpyDeviceToDevice, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (h->wloc) (void)hipFree(h->wloc);
-    h->wloc = nw;
+    if ((rc = repitch_planes(h, np, h->hwm, h->pstride))) return rc;
+    // (a shard has wloc from lx_reset on, so regrow waits for the stream here as the planes did)
+    HIPCHK(h, h->lay.wloc.regrow(np, h->pstride, Fill::all, h->stream));
     h->pstride = np;
     return 0;
 }
 
 int ensure_batch(lx_index *h, uint64_t n, uint64_t npar) {
-    if (n > h->batch_cap) {
+    Layout &l = h->lay;
+    if (n > l.batch_cap) {
         uint64_t cap = std::max<uint64_t>(n, 1024);
-        uint32_t **arrs[] = {&h->b_creator, &h->b_seq, &h->b_isfork, &h->b_rank, &h->b_tmpbr, &h->b_jmp};
-        for (uint32_t **a : arrs) {
-            if (*a) (void)hipFree(*a);
-            HIPCHK(h, dalloc(a, cap));
-        }
-        if (h->b_poff) (void)hipFree(h->b_poff);
-        HIPCHK(h, dalloc(&h->b_poff, cap + 1));
-        if (h->b_rec) (void)hipFree(h->b_rec);
-        HIPCHK(h, dalloc(&h->b_rec, (cap + 63) / 64 * 64));   // whole 64-record rounds (round-blocked SoA)
-        if (h->b_crec) (void)hipFree(h->b_crec);
-        HIPCHK(h, dalloc(&h->b_crec, (cap + 63) / 64 * 64));
+        for (DU32 *a : {&l.b_creator, &l.b_seq, &l.b_isfork, &l.b_rank, &l.b_tmpbr, &l.b_jmp}) HIPCHK(h, a->renew(cap));
+        HIPCHK(h, l.b_poff.renew(cap + 1));
+        HIPCHK(h, l.b_rec.renew((cap + 63) / 64 * 64));   // whole 64-record rounds (round-blocked SoA)
+        HIPCHK(h, l.b_crec.renew((cap + 63) / 64 * 64));
         size_t sb = 0;
         HIPCHK(h, lx::scan_tmp_bytes((uint32_t)cap, &sb));
-        if (h->scan_tmp) (void)hipFree(h->scan_tmp);
-        HIPCHK(h, hipMalloc(&h->scan_tmp, sb ? sb : 1));
-        h->scan_bytes = sb;
-        h->batch_cap = cap;
+        HIPCHK(h, l.scan_tmp.renew(sb));
+        l.batch_cap = cap;
     }
-    if (npar > h->par_cap) {
-        uint64_t cap = std::max<uint64_t>(npar, 4096);
-        if (h->b_par) (void)hipFree(h->b_par);
-        HIPCHK(h, dalloc(&h->b_par, cap));
-        h->par_cap = cap;
-    }
+    if (npar > l.b_par.cap()) HIPCHK(h, l.b_par.renew(std::max<uint64_t>(npar, 4096)));
     return 0;
 }
 
@@ -355,7 +242,7 @@ int rebuild_columns(lx_index *h) {
     }
     h->ncols = (uint32_t)cols.size();
     if (!cols.empty())
-        HIPCHK(h, hipMemcpyAsync(h->col_list, cols.data(), cols.size() * 4, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->lay.col_list, cols.data(), cols.size() * 4, hipMemcpyHostToDevice, h->stream));
     std::vector<uint32_t> off{0}, br, cr;
     for (uint32_t c = h->own_lo; c < h->own_hi; c++) {
         const auto &l = h->by_creator[c];
@@ -366,36 +253,27 @@ int rebuild_columns(lx_index *h) {
     }
     h->n_cheat = (uint32_t)cr.size();
     const std::vector<uint32_t> cr_glob = cr;   // cr becomes plane columns below (shards)
-    if (h->V > h->cheat_of_cap) {
-        if (h->cheat_of) (void)hipFree(h->cheat_of);
-        h->cheat_of = nullptr;
-        h->cheat_of_cap = 0;
-        HIPCHK(h, dalloc(&h->cheat_of, h->V));
-        h->cheat_of_cap = h->V;
-    }
+    HIPCHK(h, h->lay.cheat_of.grow(h->V));
     std::vector<int32_t> co(h->V, -1);   // alive until the sync below
     for (uint32_t k = 0; k < cr.size(); k++) co[cr[k]] = (int32_t)k;
-    HIPCHK(h, hipMemcpyAsync(h->cheat_of, co.data(), h->V * 4ull, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->lay.cheat_of, co.data(), h->V * 4ull, hipMemcpyHostToDevice, h->stream));
     uint64_t need = std::max<uint64_t>({off.size(), br.size(), 1});
-    if (need > h->cheat_cap) {
+    if (need > h->lay.cheat_off.cap()) {
         uint64_t cap = std::max<uint64_t>(need * 2, 256);
-        uint32_t **arrs[] = {&h->cheat_off, &h->cheat_br, &h->cheat_creator, &h->cheat_brl, &h->cheat_crl};
-        for (uint32_t **a : arrs) {
-            if (*a) (void)hipFree(*a);
-            HIPCHK(h, dalloc(a, cap));
-        }
-        h->cheat_cap = cap;
+        Layout &l = h->lay;
+        l.cheat_off.reset();   // (the capacity the check above reads: set last)
+        for (DU32 *a : {&l.cheat_br, &l.cheat_creator, &l.cheat_brl, &l.cheat_crl, &l.cheat_off}) HIPCHK(h, a->renew(cap));
     }
     if (h->n_cheat) {
-        HIPCHK(h, hipMemcpyAsync(h->cheat_off, off.data(), off.size() * 4, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(h->cheat_br, br.data(), br.size() * 4, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(h->cheat_creator, cr.data(), cr.size() * 4, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->lay.cheat_off, off.data(), off.size() * 4, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->lay.cheat_br, br.data(), br.size() * 4, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->lay.cheat_creator, cr.data(), cr.size() * 4, hipMemcpyHostToDevice, h->stream));
         if (h->sharded()) {
             for (auto &x : br) x = h->h_cmap[x];
             for (auto &x : cr) x = h->h_cmap[x];
         }
-        HIPCHK(h, hipMemcpyAsync(h->cheat_brl, br.data(), br.size() * 4, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(h->cheat_crl, cr.data(), cr.size() * 4, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->lay.cheat_brl, br.data(), br.size() * 4, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->lay.cheat_crl, cr.data(), cr.size() * 4, hipMemcpyHostToDevice, h->stream));
     }
     // fork-path FC tables (k_fc_fk streams every plane column; <= 64 cheaters
     // per handle, beyond that the cheater fix-up loop of k_fc<.., true>)
@@ -404,17 +282,11 @@ int rebuild_columns(lx_index *h) {
     if (h->fc_fk && h->n_cheat && h->n_cheat <= kFcFkMaxCheaters) {
         const uint32_t npc = h->sharded() ? h->nloc : h->B;
         const uint64_t cap = round_up(npc, 4);
-        if (cap > h->fk_cap) {
-            uint32_t **arrs[] = {&h->fk_w, &h->fk_c};
-            for (uint32_t **a : arrs) {
-                if (*a) (void)hipFree(*a);
-                *a = nullptr;
-            }
-            h->fk_cap = 0;
-            for (uint32_t **a : arrs) HIPCHK(h, dalloc(a, cap + cap / 2));
-            h->fk_cap = cap + cap / 2;
+        if (cap > h->lay.fk_w.cap()) {
+            h->lay.fk_w.reset();   // (the capacity the check above reads: set last)
+            for (DU32 *a : {&h->lay.fk_c, &h->lay.fk_w}) HIPCHK(h, a->renew(cap + cap / 2));
         }
-        if (!h->fk_wch) HIPCHK(h, dalloc(&h->fk_wch, kFcFkMaxCheaters));
+        HIPCHK(h, h->lay.fk_wch.grow(kFcFkMaxCheaters));
         fw.assign(cap, 0);
         fc.assign(cap, LX_NONE);
         for (uint32_t b : cols) {
@@ -426,9 +298,9 @@ int rebuild_columns(lx_index *h) {
         }
         wch.assign(kFcFkMaxCheaters, 0);
         for (uint32_t k = 0; k < h->n_cheat; k++) wch[k] = h->weights[cr_glob[k]];
-        HIPCHK(h, hipMemcpyAsync(h->fk_w, fw.data(), cap * 4, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(h->fk_c, fc.data(), cap * 4, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(h->fk_wch, wch.data(), wch.size() * 4, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->lay.fk_w, fw.data(), cap * 4, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->lay.fk_c, fc.data(), cap * 4, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->lay.fk_wch, wch.data(), wch.size() * 4, hipMemcpyHostToDevice, h->stream));
         h->fk_hi4 = (uint32_t)(cap / 4);
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -446,23 +318,23 @@ BatchArgs batch_args(lx_index *h, uint32_t n, const uint32_t *creator, const uin
     a.seq = seq;
     a.poff = poff;
     a.par = par;
-    a.ev_creator = h->ev_creator;
-    a.ev_seq = h->ev_seq;
-    a.ev_branch = h->ev_branch;
-    a.ev_bbefore = h->ev_bbefore;
-    a.ev_sp = h->ev_sp;
-    a.first_child = h->first_child;
-    a.first_root = h->first_root;
-    a.branch_first = h->branch_first;
-    a.branch_creator = h->branch_creator;
-    a.branch_len = h->branch_len;
-    a.brow = h->brow;
+    a.ev_creator = h->lay.ev_creator;
+    a.ev_seq = h->lay.ev_seq;
+    a.ev_branch = h->lay.ev_branch;
+    a.ev_bbefore = h->lay.ev_bbefore;
+    a.ev_sp = h->lay.ev_sp;
+    a.first_child = h->lay.first_child;
+    a.first_root = h->lay.first_root;
+    a.branch_first = h->lay.branch_first;
+    a.branch_creator = h->lay.branch_creator;
+    a.branch_len = h->lay.branch_len;
+    a.brow = h->lay.brow;
     a.s_cap = h->s_cap;
-    a.isfork = h->b_isfork;
-    a.rank = h->b_rank;
-    a.tmp_br = h->b_tmpbr;
-    a.jmp = h->b_jmp;
-    a.rec = h->b_rec;
+    a.isfork = h->lay.b_isfork;
+    a.rank = h->lay.b_rank;
+    a.tmp_br = h->lay.b_tmpbr;
+    a.jmp = h->lay.b_jmp;
+    a.rec = h->lay.b_rec;
     a.status = h->status;
     return a;
 }
@@ -471,22 +343,22 @@ BatchArgs batch_args(lx_index *h, uint32_t n, const uint32_t *creator, const uin
 // seg_window cuts a segment's window from it)
 IndexArgs index_args(const lx_index *h, uint32_t n, const uint32_t *poff, const uint32_t *par) {
     IndexArgs ia{};
-    ia.hb = h->hb;
-    ia.la = h->la;
+    ia.hb = h->lay.hb;
+    ia.la = h->lay.la;
     ia.stride = h->pstride;
-    ia.cmap = h->sharded() ? h->cmap : nullptr;
-    ia.lap = h->sharded() ? h->lap : nullptr;
+    ia.cmap = h->sharded() ? h->lay.cmap : nullptr;
+    ia.lap = h->sharded() ? h->lay.lap : nullptr;
     ia.lap_stride = h->stride;
     ia.batch_start = (uint32_t)h->n_events;
     ia.n = n;
-    ia.rec = h->b_rec;
-    ia.crec = h->b_crec_ok ? h->b_crec : nullptr;
+    ia.rec = h->lay.b_rec;
+    ia.crec = h->b_crec_ok ? h->lay.b_crec : nullptr;
     ia.par_in = par;
     ia.poff_in = poff;
-    ia.col_list = h->col_list;
+    ia.col_list = h->lay.col_list;
     ia.ncols = h->ncols;
-    ia.branch_first = h->branch_first;
-    ia.brow = h->brow;
+    ia.branch_first = h->lay.branch_first;
+    ia.brow = h->lay.brow;
     ia.s_cap = h->s_cap;
     ia.clk = h->d_clk;
     return ia;
@@ -557,8 +429,8 @@ void print_walker_prof(uint32_t n, const std::vector<unsigned long long> &pv) {
 int seg_walk(lx_index *h, IndexArgs ia, const WalkPlan &plan, hipStream_t s) {
     const uint32_t n = ia.n, bs = ia.batch_start, G = plan.G;
     SegArgs a{};
-    a.hb = h->hb;
-    a.la = h->la;
+    a.hb = h->lay.hb;
+    a.la = h->lay.la;
     a.stride = h->pstride;
     a.B = h->B;
     a.bs = bs;
@@ -566,27 +438,27 @@ int seg_walk(lx_index *h, IndexArgs ia, const WalkPlan &plan, hipStream_t s) {
     a.G = G;
     for (uint32_t k = 0; k < G; k++) a.seg_lo[k] = bs + (uint32_t)((uint64_t)n * k / G / 64 * 64);
     a.seg_lo[G] = bs + n;
-    a.ev_branch = h->ev_branch;
-    a.ev_seq = h->ev_seq;
-    a.branch_first = h->branch_first;
-    a.branch_len = h->branch_len;
-    a.brow = h->brow;
+    a.ev_branch = h->lay.ev_branch;
+    a.ev_seq = h->lay.ev_seq;
+    a.branch_first = h->lay.branch_first;
+    a.branch_len = h->lay.branch_len;
+    a.brow = h->lay.brow;
     a.s_cap = h->s_cap;
     a.own_seg = LX_NONE;
     a.per_rank = 1;
     int rc;
-    if ((rc = grow_scratch(h, &h->seg_jt, &h->seg_jt_cap, (uint64_t)(G + 1) * h->B)) ||
-        (rc = grow_scratch(h, &h->seg_cnt, &h->seg_cnt_cap, (uint64_t)h->B + 2 * kMaxSegments)) ||
-        (rc = grow_scratch(h, &h->seg_mf, &h->seg_mf_cap, (uint64_t)n)) ||
-        (rc = grow_scratch(h, &h->seg_plist, &h->seg_plist_cap, (uint64_t)n)) ||
-        (rc = grow_scratch(h, &h->seg_elist, &h->seg_elist_cap, (uint64_t)n)))
+    if ((rc = grow_scratch(h, h->lay.seg_jt, (uint64_t)(G + 1) * h->B)) ||
+        (rc = grow_scratch(h, h->lay.seg_cnt, (uint64_t)h->B + 2 * kMaxSegments)) ||
+        (rc = grow_scratch(h, h->lay.seg_mf, (uint64_t)n)) ||
+        (rc = grow_scratch(h, h->lay.seg_plist, (uint64_t)n)) ||
+        (rc = grow_scratch(h, h->lay.seg_elist, (uint64_t)n)))
         return rc;
-    a.jt = h->seg_jt;
-    a.cnt = h->seg_cnt;
-    a.pcount = h->seg_cnt + h->B;
-    a.pflag = h->seg_mf;
-    a.plist = h->seg_plist;
-    a.elist = h->seg_elist;
+    a.jt = h->lay.seg_jt;
+    a.cnt = h->lay.seg_cnt;
+    a.pcount = h->lay.seg_cnt + h->B;
+    a.pflag = h->lay.seg_mf;
+    a.plist = h->lay.seg_plist;
+    a.elist = h->lay.seg_elist;
     a.ecount = a.pcount + G;
     while (h->seg_ev.size() < 2 * G + 3) {
         hipEvent_t e;
@@ -599,8 +471,8 @@ int seg_walk(lx_index *h, IndexArgs ia, const WalkPlan &plan, hipStream_t s) {
     // otherwise one walk after the other
     const bool conc = plan.one_launch;
     ia.seg = 1;
-    ia.ev_branch = h->ev_branch;
-    ia.ev_seq = h->ev_seq;
+    ia.ev_branch = h->lay.ev_branch;
+    ia.ev_seq = h->lay.ev_seq;
     ia.seg_j = a.jt;
     ia.seg_flag = a.pflag;
     ia.seg_list = a.plist;
@@ -668,11 +540,11 @@ int add_batch_dev(lx_index *h, uint32_t n, const uint32_t *creator, const uint32
     HIPCHK(h, hipMemsetAsync(h->status, 0, kStatusWords * 4, s));
     HIPCHK(h, hipMemsetAsync(h->status + 8, 0xFF, 8, s));
     BatchArgs a = batch_args(h, n, creator, seq, poff, par);
-    HIPCHK(h, lx::launch_batch_prepare(a, h->scan_tmp, h->scan_bytes, s));
+    HIPCHK(h, lx::launch_batch_prepare(a, h->lay.scan_tmp, h->lay.scan_tmp.cap(), s));
     uint32_t st[16];
     uint32_t nforks = 0;
     HIPCHK(h, hipMemcpyAsync(st, h->status, sizeof st, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipMemcpyAsync(&nforks, h->b_rank + (n - 1), 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(&nforks, h->lay.b_rank + (n - 1), 4, hipMemcpyDeviceToHost, s));
     uint32_t npar32 = 0;
     HIPCHK(h, hipMemcpyAsync(&npar32, poff + n, 4, hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipStreamSynchronize(s));
@@ -700,7 +572,7 @@ int add_batch_dev(lx_index *h, uint32_t n, const uint32_t *creator, const uint32
     WalkEpoch we = h->walk_epoch();
     we.B = B_new;
     h->b_crec_ok = walk_crec_ok(we, h->crec_opt);
-    a.crec = h->b_crec_ok ? h->b_crec : nullptr;
+    a.crec = h->b_crec_ok ? h->lay.b_crec : nullptr;
     // pointer jumping along in-batch self-parent chains: a chain has at most
     // min(n, max seq) events, ceil(log2) + 1 rounds resolve it (k_finalize flags
     // an unresolved event, checked below); none without forks
@@ -709,8 +581,8 @@ int add_batch_dev(lx_index *h, uint32_t n, const uint32_t *creator, const uint32
     HIPCHK(h, lx::launch_batch_finish(a, a.nofork ? 0u : rounds + 1, s));
     if (nforks) {
         std::vector<uint32_t> cr(nforks), fs(nforks);
-        HIPCHK(h, hipMemcpyAsync(cr.data(), h->branch_creator + h->B, nforks * 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipMemcpyAsync(fs.data(), h->branch_first + h->B, nforks * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipMemcpyAsync(cr.data(), h->lay.branch_creator + h->B, nforks * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipMemcpyAsync(fs.data(), h->lay.branch_first + h->B, nforks * 4, hipMemcpyDeviceToHost, s));
         HIPCHK(h, hipStreamSynchronize(s));
         for (uint32_t i = 0; i < nforks; i++) {
             h->h_branch_creator.push_back(cr[i]);
@@ -721,7 +593,7 @@ int add_batch_dev(lx_index *h, uint32_t n, const uint32_t *creator, const uint32
         }
         if (h->sharded()) {
             if ((rc = grow_local(h, h->nloc))) return rc;
-            HIPCHK(h, hipMemcpyAsync(h->cmap + h->B, h->h_cmap.data() + h->B, nforks * 4ull, hipMemcpyHostToDevice, s));
+            HIPCHK(h, hipMemcpyAsync(h->lay.cmap + h->B, h->h_cmap.data() + h->B, nforks * 4ull, hipMemcpyHostToDevice, s));
         }
     }
     h->B = B_new;
@@ -731,20 +603,22 @@ int add_batch_dev(lx_index *h, uint32_t n, const uint32_t *creator, const uint32
 
     const size_t prof_n = (size_t)kProfBlocks * kProfWaves * kProfSlots;
     if (!h->d_clk) {
-        HIPCHK(h, hipMalloc(&h->d_clk, (1 + 3ull * kClkBlocks) * 8));
+        HIPCHK(h, h->d_clk.renew(1 + 3ull * kClkBlocks));
         HIPCHK(h, hipMemsetAsync(h->d_clk, 0, (1 + 3ull * kClkBlocks) * 8, s));
     }
     IndexArgs ia = index_args(h, n, poff, par);
     const WalkPlan plan = walk_plan(h->walk_epoch(), n);   // (a row-segment rank makes its own, rs_begin)
+    DevBuf<unsigned long long> d_prof;
     if (h->prof) {
-        HIPCHK(h, hipMalloc(&ia.prof, prof_n * 8));
+        HIPCHK(h, d_prof.renew(prof_n));
+        ia.prof = d_prof;
         HIPCHK(h, hipMemsetAsync(ia.prof, 0, prof_n * 8, s));
     }
     HIPCHK(h, hipEventRecord(h->ev[1], s));
     if (h->rowseg()) {
         if ((rc = rs_planes(h, n))) return rc;   // own rows only (+ the virtual bases)
-        ia.hb = h->hb;
-        ia.la = h->la;
+        ia.hb = h->lay.hb;
+        ia.la = h->lay.la;
         if ((rc = rs_begin(h, ia, s))) return rc;
     } else if (plan.G && h->segments > 1) {   // option segments
         if ((rc = seg_walk(h, ia, plan, s))) return rc;
@@ -753,19 +627,19 @@ int add_batch_dev(lx_index *h, uint32_t n, const uint32_t *creator, const uint32
         // few branches, no forks: HB by frontier doubling in one workgroup
         // (the walker's time is levels x pass, and such epochs are deep chains)
         DblArgs da{};
-        da.hb = h->hb;
-        da.la = h->la;
+        da.hb = h->lay.hb;
+        da.la = h->lay.la;
         da.stride = h->pstride;
         da.bs = (uint32_t)h->n_events;
         da.n = n;
         da.B = h->B;
-        da.rec = h->b_rec;
+        da.rec = h->lay.b_rec;
         da.par = par;
         da.poff = poff;
-        da.ev_branch = h->ev_branch;
-        da.ev_seq = h->ev_seq;
-        da.branch_first = h->branch_first;
-        da.brow = h->brow;
+        da.ev_branch = h->lay.ev_branch;
+        da.ev_seq = h->lay.ev_seq;
+        da.branch_first = h->lay.branch_first;
+        da.brow = h->lay.brow;
         da.s_cap = h->s_cap;
         HIPCHK(h, lx::launch_dbl(da, s));
     } else if (plan.G) {   // side-by-side segments worth it (walk_seg_pick)
@@ -778,23 +652,22 @@ int add_batch_dev(lx_index *h, uint32_t n, const uint32_t *creator, const uint32
         std::vector<unsigned long long> pv(prof_n);
         HIPCHK(h, hipMemcpyAsync(pv.data(), ia.prof, prof_n * 8, hipMemcpyDeviceToHost, s));
         HIPCHK(h, hipStreamSynchronize(s));
-        HIPCHK(h, hipFree(ia.prof));
         print_walker_prof(n, pv);
     }
     if (h->B > h->V && h->n_cheat && !h->rowseg()) {   // a row-segment rank marks its rows at lx_rowseg_finish
         MarkArgs m{};
-        m.hb = h->hb;
+        m.hb = h->lay.hb;
         m.stride = h->pstride;
-        m.cmap = h->sharded() ? h->cmap : nullptr;
+        m.cmap = h->sharded() ? h->lay.cmap : nullptr;
         m.batch_start = (uint32_t)h->n_events;
         m.n = n;
         m.V = h->V;
-        m.ev_branch = h->ev_branch;
-        m.ev_bbefore = h->ev_bbefore;
-        m.branch_first = h->branch_first;
+        m.ev_branch = h->lay.ev_branch;
+        m.ev_bbefore = h->lay.ev_bbefore;
+        m.branch_first = h->lay.branch_first;
         m.n_cheat = h->n_cheat;
-        m.cheat_off = h->cheat_off;
-        m.cheat_br = h->cheat_br;
+        m.cheat_off = h->lay.cheat_off;
+        m.cheat_br = h->lay.cheat_br;
         HIPCHK(h, lx::launch_marks(m, s));
     }
     if (!h->sharded() && !h->rowseg() && h->la_tail) {
@@ -827,15 +700,15 @@ int lx_fc_args(lx_index *h, uint64_t n, const uint32_t *a, const uint32_t *b, ui
     if (h->rowseg() && h->rs_state != 4)
         return h->fail(LX_ERR_STATE, "row-segment rank: ForklessCause before lx_rowseg_finish");
     FcArgs f{};
-    f.hb = h->hb;
-    f.la = h->la;
+    f.hb = h->lay.hb;
+    f.la = h->lay.la;
     f.stride = h->pstride;
     f.n_events = h->rowseg() ? h->rs_hi : (uint32_t)h->n_events;
     f.ev_lo = h->rowseg() ? h->rs_lo : 0u;
-    f.b_stamp = h->rowseg() ? h->rs_stamp : nullptr;
+    f.b_stamp = h->rowseg() ? h->lay.rs_stamp : nullptr;
     f.n_all = (uint32_t)h->n_events;
-    f.la_recv = h->rowseg() ? h->rs_rla : nullptr;
-    f.b_slot = h->rowseg() ? h->rs_lslot : nullptr;
+    f.la_recv = h->rowseg() ? h->lay.rs_rla : nullptr;
+    f.b_slot = h->rowseg() ? h->lay.rs_lslot : nullptr;
     f.b_arrived = 2 * h->rs_gen + 1;
     f.n = n;
     f.qa = a;
@@ -843,32 +716,32 @@ int lx_fc_args(lx_index *h, uint64_t n, const uint32_t *a, const uint32_t *b, ui
     f.out = out;
     f.partial = partial;
     if (h->sharded()) {
-        f.wpad = h->wloc;     // local columns: own originals first
+        f.wpad = h->lay.wloc;     // local columns: own originals first
         f.vlo4 = 0;
         f.vhi4 = (h->own_hi - h->own_lo + 3) / 4;
-        f.cmap = h->cmap;
+        f.cmap = h->lay.cmap;
     } else {
-        f.wpad = h->wpad;
+        f.wpad = h->lay.wpad;
         f.vlo4 = h->own_lo / 4;
         f.vhi4 = (h->own_hi + 3) / 4;
         f.cmap = nullptr;
     }
-    f.cheat_brl = h->cheat_brl;
-    f.cheat_crl = h->cheat_crl;
-    f.fk_w = h->fk_w;
-    f.fk_c = h->fk_c;
-    f.fk_wch = h->fk_wch;
+    f.cheat_brl = h->lay.cheat_brl;
+    f.cheat_crl = h->lay.cheat_crl;
+    f.fk_w = h->lay.fk_w;
+    f.fk_c = h->lay.fk_c;
+    f.fk_wch = h->lay.fk_wch;
     f.fk_hi4 = h->fk_hi4;
     f.quorum = h->quorum;
-    f.ev_branch = h->ev_branch;
-    f.ev_creator = h->ev_creator;
+    f.ev_branch = h->lay.ev_branch;
+    f.ev_creator = h->lay.ev_creator;
     f.n_cheat = h->n_cheat;
-    f.cheat_off = h->cheat_off;
-    f.cheat_br = h->cheat_br;
-    f.cheat_creator = h->cheat_creator;
+    f.cheat_off = h->lay.cheat_off;
+    f.cheat_br = h->lay.cheat_br;
+    f.cheat_creator = h->lay.cheat_creator;
     f.own_lo = h->own_lo;
     f.own_hi = h->own_hi;
-    f.branch_creator = h->branch_creator;
+    f.branch_creator = h->lay.branch_creator;
     f.status = h->status;
     // early exit (k_fc_early: fork-free whole rows of more than 512 columns --
     // launch_fc's 64-lane width, the gate matches what runs): rounds of the
@@ -892,15 +765,12 @@ int lx_fc_args(lx_index *h, uint64_t n, const uint32_t *a, const uint32_t *b, ui
             if (!h->d_fc_full) {
                 // zeroed and synchronized before any launch can count into it,
                 // whatever stream runs that launch
-                unsigned long long *p = nullptr;
-                HIPCHK(h, hipMalloc((void **)&p, 32));
+                DevBuf<unsigned long long> p;
+                HIPCHK(h, p.renew(4));
                 hipError_t e = hipMemsetAsync(p, 0, 32, h->stream);
                 if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-                if (e != hipSuccess) {
-                    (void)hipFree(p);
-                    return h->hip(e, "ForklessCause early-exit counters");
-                }
-                h->d_fc_full = p;
+                if (e != hipSuccess) return h->hip(e, "ForklessCause early-exit counters");
+                h->d_fc_full = std::move(p);
             }
             f.early = 1;
             f.early_rest = (uint32_t)(wt - w128);
@@ -943,30 +813,24 @@ int ensure_shard_rows(lx_index *h) {
     if (h->sc_events == h->n_events && h->sc_B == h->B) return 0;
     const uint32_t n = (uint32_t)h->n_events;
     const uint32_t G = h->shard_count;
-    if (n > h->sc_cap || h->sc_rows.size() != G) {
-        for (uint32_t *p : h->sc_rows)
-            if (p) (void)hipFree(p);
-        h->sc_rows.assign(G, nullptr);
+    if (n > h->lay.sc_flag.cap() || h->lay.sc_rows.size() != G) {
+        h->lay.sc_rows = std::vector<DU32>(G);
         uint64_t cap = std::max<uint64_t>(n, 4096);
-        for (uint32_t q = 0; q < G; q++) HIPCHK(h, dalloc(&h->sc_rows[q], cap));
-        if (h->sc_flag) (void)hipFree(h->sc_flag);
-        if (h->sc_pos) (void)hipFree(h->sc_pos);
-        HIPCHK(h, dalloc(&h->sc_flag, cap));
-        HIPCHK(h, dalloc(&h->sc_pos, cap));
+        for (DU32 &r : h->lay.sc_rows) HIPCHK(h, r.renew(cap));
+        h->lay.sc_flag.reset();   // (the capacity the check above reads: set last)
+        HIPCHK(h, h->lay.sc_pos.renew(cap));
         size_t sb = 0;
         HIPCHK(h, lx::scan_tmp_bytes((uint32_t)cap, &sb));
-        if (h->sc_tmp) (void)hipFree(h->sc_tmp);
-        HIPCHK(h, hipMalloc(&h->sc_tmp, sb ? sb : 1));
-        h->sc_tmp_bytes = sb;
-        h->sc_cap = cap;
+        HIPCHK(h, h->lay.sc_tmp.renew(sb));
+        HIPCHK(h, h->lay.sc_flag.renew(cap));
     }
-    h->sc_nrows.assign(G, 0);
+    h->lay.sc_nrows.assign(G, 0);
     for (uint32_t q = 0; q < G; q++) {
         uint32_t lo, hi;
         shard_bounds(h, q, &lo, &hi);
-        HIPCHK(h, lx::launch_shard_rows(h->ev_branch, h->branch_creator, n, lo, hi, h->sc_flag, h->sc_pos, h->sc_tmp,
-                                        h->sc_tmp_bytes, h->sc_rows[q], h->stream));
-        if (n) HIPCHK(h, hipMemcpyAsync(&h->sc_nrows[q], h->sc_pos + (n - 1), 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, lx::launch_shard_rows(h->lay.ev_branch, h->lay.branch_creator, n, lo, hi, h->lay.sc_flag,
+                                        h->lay.sc_pos, h->lay.sc_tmp, h->lay.sc_tmp.cap(), h->lay.sc_rows[q], h->stream));
+        if (n) HIPCHK(h, hipMemcpyAsync(&h->lay.sc_nrows[q], h->lay.sc_pos + (n - 1), 4, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
     }
     if (int rc = upload_cols(h)) return rc;
@@ -978,7 +842,7 @@ int ensure_shard_rows(lx_index *h) {
 
 // the column lists alone (the incremental exchange lists its rows itself)
 int ensure_shard_cols(lx_index *h) {
-    if (h->sc_cols && h->sc_cols_B == h->B) return 0;
+    if (h->lay.sc_cols && h->sc_cols_B == h->B) return 0;
     if (int rc = upload_cols(h)) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return 0;
@@ -994,13 +858,9 @@ int upload_cols(lx_index *h) {
         all.insert(all.end(), c.begin(), c.end());
         h->sc_col_off.push_back((uint32_t)all.size());
     }
-    if (h->sc_cols) {
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        (void)hipFree(h->sc_cols);
-    }
-    HIPCHK(h, dalloc(&h->sc_cols, all.size()));
+    HIPCHK(h, h->lay.sc_cols.renew(all.size(), h->stream, true));
     if (!all.empty())
-        HIPCHK(h, hipMemcpyAsync(h->sc_cols, all.data(), all.size() * 4, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->lay.sc_cols, all.data(), all.size() * 4, hipMemcpyHostToDevice, h->stream));
     h->sc_cols_B = h->B;
     return 0;
 }
@@ -1013,25 +873,25 @@ int read_u32(lx_index *h, const uint32_t *dev, uint32_t *out) {
 // the LowestAfter fills of the events added since the last flush (rollback and write-back)
 UnfillArgs unfill_args(lx_index *h) {
     UnfillArgs u{};
-    u.hb = h->hb;
-    u.la = h->la;
+    u.hb = h->lay.hb;
+    u.la = h->lay.la;
     u.stride = h->pstride;
-    u.cmap = h->sharded() ? h->cmap : nullptr;
-    u.lap = h->sharded() ? h->lap : nullptr;
+    u.cmap = h->sharded() ? h->lay.cmap : nullptr;
+    u.lap = h->sharded() ? h->lay.lap : nullptr;
     u.lap_stride = h->stride;
     u.lo = (uint32_t)h->n_flushed;
     u.hi = (uint32_t)h->n_events;
     u.B = h->B;
-    u.ev_seq = h->ev_seq;
-    u.ev_branch = h->ev_branch;
-    u.ev_bbefore = h->ev_bbefore;
-    u.ev_sp = h->ev_sp;
-    u.ev_creator = h->ev_creator;
-    u.first_child = h->first_child;
-    u.first_root = h->first_root;
-    u.branch_len = h->branch_len;
-    u.branch_first = h->branch_first;
-    u.brow = h->brow;
+    u.ev_seq = h->lay.ev_seq;
+    u.ev_branch = h->lay.ev_branch;
+    u.ev_bbefore = h->lay.ev_bbefore;
+    u.ev_sp = h->lay.ev_sp;
+    u.ev_creator = h->lay.ev_creator;
+    u.first_child = h->lay.first_child;
+    u.first_root = h->lay.first_root;
+    u.branch_len = h->lay.branch_len;
+    u.branch_first = h->lay.branch_first;
+    u.brow = h->lay.brow;
     u.s_cap = h->s_cap;
     u.B_keep = h->B_flushed;
     return u;
@@ -1039,39 +899,30 @@ UnfillArgs unfill_args(lx_index *h) {
 
 // ---- write-back helpers
 int ensure_wb(lx_index *h, uint64_t n) {
-    if (n <= h->wb_cap && h->wb_flag) return 0;
-    void *keep_buf = h->wb_buf;
-    uint64_t keep_cap = h->wb_buf_cap;
-    h->wb_buf = nullptr;
-    free_wb(h);
-    h->wb_buf = (uint32_t *)keep_buf;
-    h->wb_buf_cap = keep_cap;
+    if (n <= h->lay.wb_flag.cap() && h->lay.wb_flag) return 0;
+    Layout &l = h->lay;
+    h->wb_ready = false;
+    l.wb_flag.reset();   // (the capacity the check above reads: set last; wb_buf stays)
     const uint64_t cap = std::max<uint64_t>(n, 4096);
-    HIPCHK(h, dalloc(&h->wb_flag, cap));
-    HIPCHK(h, dalloc(&h->wb_pos, cap));
-    HIPCHK(h, dalloc(&h->wb_la_rows, cap));
-    HIPCHK(h, dalloc(&h->wb_hb_rows, cap));
-    HIPCHK(h, dalloc(&h->wb_len, cap + 1));
-    HIPCHK(h, dalloc(&h->wb_la_off, cap + 1));
-    HIPCHK(h, dalloc(&h->wb_hb_off, cap + 1));
+    for (DU32 *b : {&l.wb_pos, &l.wb_la_rows, &l.wb_hb_rows}) HIPCHK(h, b->renew(cap));
+    for (auto *b : {&l.wb_len, &l.wb_la_off, &l.wb_hb_off}) HIPCHK(h, b->renew(cap + 1));
     size_t tb = 0;
     HIPCHK(h, lx::persist_tmp_bytes((uint32_t)cap, &tb));
-    HIPCHK(h, hipMalloc(&h->wb_tmp, tb ? tb : 1));
-    h->wb_tmp_bytes = tb;
-    h->wb_cap = cap;
+    HIPCHK(h, l.wb_tmp.renew(tb));
+    HIPCHK(h, l.wb_flag.renew(cap));
     return 0;
 }
 
 RowsArgs rows_args(lx_index *h, uint32_t hb, const uint32_t *rows, uint32_t n) {
     RowsArgs a{};
-    a.plane = hb ? h->hb : h->la;
+    a.plane = hb ? h->lay.hb : h->lay.la;
     a.stride = h->stride;
     a.rows = rows;
     a.n = n;
     a.B = h->B;
-    a.ev_bbefore = h->ev_bbefore;
-    a.ev_branch = h->ev_branch;
-    a.branch_first = h->branch_first;
+    a.ev_bbefore = h->lay.ev_bbefore;
+    a.ev_branch = h->lay.ev_branch;
+    a.branch_first = h->lay.branch_first;
     a.hb = hb;
     return a;
 }
@@ -1089,19 +940,13 @@ int rows_to_host(lx_index *h, uint32_t hb, const uint32_t *rows, const uint64_t 
     uint64_t row_max = 0;
     for (uint32_t i = 0; i < n; i++) row_max = std::max(row_max, off[i + 1] - off[i]);
     const uint64_t want = std::max(std::min(off[n], kWbChunk), row_max);
-    if (want > h->wb_buf_cap) {
-        if (h->wb_buf) (void)hipFree(h->wb_buf);
-        h->wb_buf = nullptr;
-        h->wb_buf_cap = 0;
-        HIPCHK(h, dalloc(&h->wb_buf, (want + 3) / 4));
-        h->wb_buf_cap = want;
-    }
+    if (want > h->lay.wb_buf.bytes()) HIPCHK(h, h->lay.wb_buf.renew((want + 3) / 4));
     for (uint32_t i0 = 0; i0 < n;) {
         uint32_t i1 = i0 + 1;
-        while (i1 < n && off[i1 + 1] - off[i0] <= h->wb_buf_cap) i1++;
+        while (i1 < n && off[i1 + 1] - off[i0] <= h->lay.wb_buf.bytes()) i1++;
         RowsArgs a = rows_args(h, hb, rows + i0, i1 - i0);
-        HIPCHK(h, lx::launch_encode_rows(a, off_dev + i0, off[i0], h->wb_buf, h->stream));
-        HIPCHK(h, hipMemcpyAsync(bytes + off[i0], h->wb_buf, off[i1] - off[i0], hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, lx::launch_encode_rows(a, off_dev + i0, off[i0], h->lay.wb_buf, h->stream));
+        HIPCHK(h, hipMemcpyAsync(bytes + off[i0], h->lay.wb_buf, off[i1] - off[i0], hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
         i0 = i1;
     }
@@ -1134,7 +979,7 @@ void rlp_list(std::string &o, const std::string &payload) {
 
 int branches_info_rlp(lx_index *h, std::string *out) {
     std::vector<uint32_t> len(h->B);
-    HIPCHK(h, hipMemcpyAsync(len.data(), h->branch_len, h->B * 4ull, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(len.data(), h->lay.branch_len, h->B * 4ull, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     std::string last, cr, by, body;
     for (uint32_t b = 0; b < h->B; b++) {
@@ -1158,19 +1003,12 @@ int branches_info_rlp(lx_index *h, std::string *out) {
 constexpr uint64_t kFcPinnedMax = 1u << 16;
 
 int ensure_qp(lx_index *h, uint64_t bytes, uint8_t **host, uint8_t **dev) {
-    if (bytes > h->qp_cap || !h->qp) {
-        if (h->qp) {
-            HIPCHK(h, hipStreamSynchronize(h->stream));
-            (void)hipHostFree(h->qp);
-        }
-        h->qp = h->qp_dev = nullptr;
-        h->qp_cap = 0;
-        const uint64_t cap = std::max<uint64_t>(bytes, 1u << 16);
-        HIPCHK(h, hipHostMalloc((void **)&h->qp, cap, hipHostMallocMapped));
+    if (bytes > h->qp.cap() || !h->qp) {
+        h->qp_dev = nullptr;
+        HIPCHK(h, h->qp.renew(std::max<uint64_t>(bytes, 1u << 16), h->stream, true));
         void *d = nullptr;
         HIPCHK(h, hipHostGetDevicePointer(&d, h->qp, 0));   // once per buffer, not per call
         h->qp_dev = static_cast<uint8_t *>(d);
-        h->qp_cap = cap;
     }
     *host = h->qp;
     *dev = h->qp_dev;
@@ -1186,13 +1024,13 @@ int hm_sync(lx_index *h) {
     HIPCHK(h, hipStreamSynchronize(h->stream));
     const uint64_t n = h->n_events, lo = std::min(h->hm_n, n);
     rawvec<uint32_t> *v[] = {&h->hm_creator, &h->hm_seq, &h->hm_branch, &h->hm_bbefore};
-    const uint32_t *d[] = {h->ev_creator, h->ev_seq, h->ev_branch, h->ev_bbefore};
+    const uint32_t *d[] = {h->lay.ev_creator, h->lay.ev_seq, h->lay.ev_branch, h->lay.ev_bbefore};
     for (int k = 0; k < 4; k++) {
         v[k]->resize(n);
         if (n > lo) HIPCHK(h, hipMemcpy(v[k]->data() + lo, d[k] + lo, (n - lo) * 4, hipMemcpyDeviceToHost));
     }
     h->hm_blen.resize(h->B);
-    HIPCHK(h, hipMemcpy(h->hm_blen.data(), h->branch_len, h->B * 4ull, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(h->hm_blen.data(), h->lay.branch_len, h->B * 4ull, hipMemcpyDeviceToHost));
     h->hm_n = n;
     h->hm_ok = true;
     return 0;
@@ -1207,24 +1045,12 @@ int stage_slot(lx_index *h, uint64_t words, uint32_t **out, int *slot) {
     const int k = (int)h->st_next;
     h->st_next = (h->st_next + 1) % lx_index::kSlots;
     if (h->st_used[k]) HIPCHK(h, hipEventSynchronize(h->st_copied[k]));
-    if (words > h->st_pin_cap[k] || words > h->st_dev_cap[k]) {
+    if (words > h->st_pin[k].cap() || words > h->st_dev[k].cap()) {
         const uint64_t cap = std::max<uint64_t>(words + words / 2, 16384);
         HIPCHK(h, hipStreamSynchronize(h->stream));   // every copy and kernel that read a slot
         for (int j = 0; j < lx_index::kSlots; j++) {
-            if (cap > h->st_pin_cap[j]) {
-                if (h->st_pin[j]) (void)hipHostFree(h->st_pin[j]);
-                h->st_pin[j] = nullptr;
-                h->st_pin_cap[j] = 0;
-                HIPCHK(h, hipHostMalloc((void **)&h->st_pin[j], cap * 4, hipHostMallocDefault));
-                h->st_pin_cap[j] = cap;
-            }
-            if (cap > h->st_dev_cap[j]) {
-                if (h->st_dev[j]) (void)hipFree(h->st_dev[j]);
-                h->st_dev[j] = nullptr;
-                h->st_dev_cap[j] = 0;
-                HIPCHK(h, dalloc(&h->st_dev[j], cap));
-                h->st_dev_cap[j] = cap;
-            }
+            HIPCHK(h, h->st_pin[j].grow(cap));
+            HIPCHK(h, h->st_dev[j].grow(cap));
         }
     }
     *out = h->st_pin[k];
@@ -1311,8 +1137,8 @@ int flush_pending(lx_index *h) {
     }
     SmallArgs &a = h->sm_inl.a;
     a = SmallArgs{};
-    a.hb = h->hb;
-    a.la = h->la;
+    a.hb = h->lay.hb;
+    a.la = h->lay.la;
     a.stride = h->pstride;
     a.bs = (uint32_t)bs;
     a.n = n;
@@ -1331,17 +1157,17 @@ int flush_pending(lx_index *h) {
     a.o_ncreator = (uint32_t)(ncreator - img);
     a.o_blen = (uint32_t)(blen - img);
     a.n_blen = n_blen;
-    a.ev_creator = h->ev_creator;
-    a.ev_seq = h->ev_seq;
-    a.ev_branch = h->ev_branch;
-    a.ev_bbefore = h->ev_bbefore;
-    a.ev_sp = h->ev_sp;
-    a.first_child = h->first_child;
-    a.first_root = h->first_root;
-    a.branch_first = h->branch_first;
-    a.branch_creator = h->branch_creator;
-    a.branch_len = h->branch_len;
-    a.brow = h->brow;
+    a.ev_creator = h->lay.ev_creator;
+    a.ev_seq = h->lay.ev_seq;
+    a.ev_branch = h->lay.ev_branch;
+    a.ev_bbefore = h->lay.ev_bbefore;
+    a.ev_sp = h->lay.ev_sp;
+    a.first_child = h->lay.first_child;
+    a.first_root = h->lay.first_root;
+    a.branch_first = h->lay.branch_first;
+    a.branch_creator = h->lay.branch_creator;
+    a.branch_len = h->lay.branch_len;
+    a.brow = h->lay.brow;
     a.s_cap = h->s_cap;
     a.mask = B > h->V ? 1u : 0u;
     if (h->small_timing) HIPCHK(h, hipEventRecord(h->ev[1], s));
@@ -1354,17 +1180,17 @@ int flush_pending(lx_index *h) {
     if (h->small_timing) HIPCHK(h, hipEventRecord(h->ev[2], s));
     if (B > h->V && h->n_cheat) {
         MarkArgs m{};
-        m.hb = h->hb;
+        m.hb = h->lay.hb;
         m.stride = h->pstride;
         m.batch_start = (uint32_t)bs;
         m.n = n;
         m.V = h->V;
-        m.ev_branch = h->ev_branch;
-        m.ev_bbefore = h->ev_bbefore;
-        m.branch_first = h->branch_first;
+        m.ev_branch = h->lay.ev_branch;
+        m.ev_bbefore = h->lay.ev_bbefore;
+        m.branch_first = h->lay.branch_first;
         m.n_cheat = h->n_cheat;
-        m.cheat_off = h->cheat_off;
-        m.cheat_br = h->cheat_br;
+        m.cheat_off = h->lay.cheat_off;
+        m.cheat_br = h->lay.cheat_br;
         HIPCHK(h, lx::launch_marks(m, s));
     }
     h->pend_n = 0;
@@ -1396,30 +1222,30 @@ int flush_add1_row(lx_index *h, uint32_t a, uint32_t *evk_dev, uint32_t n_slots,
             r.par[np++] = o.y;
         }
     if (np != e.q0.w) return 1;
-    r.hb = h->hb;
-    r.la = h->la;
+    r.hb = h->lay.hb;
+    r.la = h->lay.la;
     r.stride = h->pstride;
     r.a = a;
     r.e = e;
     r.blen = h->hm_blen[e.q0.x];
     r.B = h->B;
     r.w_br = h->weights[e.q0.x];
-    r.ev_creator = h->ev_creator;
-    r.ev_seq = h->ev_seq;
-    r.ev_branch = h->ev_branch;
-    r.ev_bbefore = h->ev_bbefore;
-    r.ev_sp = h->ev_sp;
-    r.first_child = h->first_child;
-    r.first_root = h->first_root;
-    r.branch_len = h->branch_len;
-    r.brow = h->brow;
-    r.branch_first = h->branch_first;
+    r.ev_creator = h->lay.ev_creator;
+    r.ev_seq = h->lay.ev_seq;
+    r.ev_branch = h->lay.ev_branch;
+    r.ev_bbefore = h->lay.ev_bbefore;
+    r.ev_sp = h->lay.ev_sp;
+    r.first_child = h->lay.first_child;
+    r.first_root = h->lay.first_root;
+    r.branch_len = h->lay.branch_len;
+    r.brow = h->lay.brow;
+    r.branch_first = h->lay.branch_first;
     r.s_cap = h->s_cap;
     r.evk = evk_dev;
     r.n_slots = n_slots;
     r.tag = tag_dev;
     r.out = out_dev;
-    r.wpad = h->wpad;
+    r.wpad = h->lay.wpad;
     r.quorum = h->quorum;
     r.psum = psum_dev;
     if (delta) {
@@ -1692,7 +1518,7 @@ int lx_create(const lx_config *cfg, lx_index **out) {
     }
     if (h->shard_rank >= h->shard_count) { delete h; return LX_ERR_ARG; }
     if (hipSetDevice(h->device) != hipSuccess || hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipMalloc((void **)&h->status, kStatusWords * 4) != hipSuccess ||
+        h->status.renew(kStatusWords) != hipSuccess ||
         hipMemset(h->status, 0, kStatusWords * 4) != hipSuccess) {
         delete h;
         return LX_ERR_HIP;
@@ -1726,28 +1552,17 @@ void lx_destroy(lx_index *h) {
     (void)hipSetDevice(h->device);
     srv_stop(h);
     if (h->srv_stream) (void)hipStreamDestroy(h->srv_stream);
-    if (h->srv_host) (void)hipHostFree(h->srv_host);
     (void)hipStreamSynchronize(h->stream);
     fcc_destroy(h);
     free_all(h);
-    if (h->status) (void)hipFree(h->status);
     for (auto &e : h->ev)
         if (e) (void)hipEventDestroy(e);
     for (auto &e : h->st_copied)
         if (e) (void)hipEventDestroy(e);
     for (auto &e : h->seg_ev) (void)hipEventDestroy(e);
-    for (auto *p : h->st_pin)
-        if (p) (void)hipHostFree(p);
-    for (auto *p : h->st_dev)
-        if (p) (void)hipFree(p);
-    if (h->qp) (void)hipHostFree(h->qp);
-    if (h->ld_buf) (void)hipFree(h->ld_buf);
-    if (h->d_fc_full) (void)hipFree(h->d_fc_full);
-    if (h->d_clk) (void)hipFree(h->d_clk);
-    for (void *q : {(void *)h->fcs_flag, (void *)h->fcs_pos, h->fcs_tmp})
-        if (q) (void)hipFree(q);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
+    const hipStream_t stream = h->stream;
+    delete h;   // with the buffers that lived as long as the handle
+    if (stream) (void)hipStreamDestroy(stream);
 }
 
 const char *lx_last_error(const lx_index *h) { return h ? h->err.c_str() : "null handle"; }
@@ -1849,17 +1664,16 @@ int lx_set_option(lx_index *h, const char *name, int64_t value) {
         if (value) {
             HIPCHK(h, set_dev(h->device));
             HIPCHK(h, hipStreamSynchronize(h->stream));
-            const uint64_t n = (h->batch_cap + 63) / 64 * 64;
-            auto move = [&](auto **b) -> int {
-                if (!*b) return 0;
-                std::remove_reference_t<decltype(*b)> nb = nullptr;
-                HIPCHK(h, dalloc(&nb, n));
-                (void)hipFree(*b);
-                *b = nb;
+            const uint64_t n = (h->lay.batch_cap + 63) / 64 * 64;
+            auto move = [&](auto &b) -> int {
+                if (!b) return 0;
+                std::remove_reference_t<decltype(b)> nb;
+                HIPCHK(h, nb.renew(n));
+                b = std::move(nb);
                 return 0;
             };
-            if (int rc = move(&h->b_rec)) return rc;
-            if (int rc = move(&h->b_crec)) return rc;
+            if (int rc = move(h->lay.b_rec)) return rc;
+            if (int rc = move(h->lay.b_crec)) return rc;
         }
     } else if (k == "dbl") {
         h->dbl = value != 0;
@@ -1942,7 +1756,7 @@ int lx_reset(lx_index *h, uint32_t nv, const uint32_t *w) {
         h->s_cap = 0;
         h->pstride = h->sharded() ? want_p : 0;
         if ((rc = grow_branches(h, want_stride))) return rc;
-        if (h->sharded()) HIPCHK(h, dalloc(&h->wloc, h->pstride));
+        if (h->sharded()) HIPCHK(h, h->lay.wloc.renew(h->pstride));
         uint32_t s0 = 1024;
         if (h->cap_hint) s0 = (uint32_t)std::min<uint64_t>(h->cap_hint / nv + 64, 0x7FFFFFFF);
         if ((rc = grow_scap(h, s0))) return rc;
@@ -1951,7 +1765,7 @@ int lx_reset(lx_index *h, uint32_t nv, const uint32_t *w) {
     } else if (h->hwm && h->rowseg()) {
         // a row-segment rank: its own rows are rewritten (HB by the walk and the
         // fix-up, LA zeroed at the batch, rs_begin); only the metadata resets
-        HIPCHK(h, lx::launch_fill_u32(h->first_child, h->hwm, LX_NONE, h->stream));
+        HIPCHK(h, lx::launch_fill_u32(h->lay.first_child, h->hwm, LX_NONE, h->stream));
         h->hwm = 0;
     } else if (h->hwm) {
         // HB: the walker rewrites the original columns of every new event's row
@@ -1962,23 +1776,25 @@ int lx_reset(lx_index *h, uint32_t nv, const uint32_t *w) {
         const uint32_t no = h->sharded() ? norig : nv;
         const uint32_t used = std::min(h->pcols_used, h->pstride);
         if (used > no)
-            HIPCHK(h, hipMemset2DAsync(h->hb + no, (size_t)h->pstride * 4, 0, (size_t)(used - no) * 4, h->hwm, h->stream));
+            HIPCHK(h, hipMemset2DAsync(h->lay.hb + no, (size_t)h->pstride * 4, 0, (size_t)(used - no) * 4, h->hwm,
+                                       h->stream));
         // a shard's query plane is rewritten whole by the exchange (full blocks,
         // zeros included) before any ForklessCause: only its fill target needs zeroing
-        if (h->lap) {
-            HIPCHK(h, hipMemsetAsync(h->lap, 0, (uint64_t)h->pstride * h->s_cap * h->stride * 4, h->stream));
+        if (h->lay.lap) {
+            HIPCHK(h, hipMemsetAsync(h->lay.lap, 0, (uint64_t)h->pstride * h->s_cap * h->stride * 4, h->stream));
         } else if (h->la_tail) {
             // every entry (x, j < B) of a row is rewritten after its batch (fill or
             // tail, la_tail): only fork-branch columns of old rows need zeroing
             if (used > no)
-                HIPCHK(h, hipMemset2DAsync(h->la + no, (size_t)h->pstride * 4, 0, (size_t)(used - no) * 4, h->hwm, h->stream));
-            if (h->tail_zw && h->tail_dirty)
-                HIPCHK(h, hipMemsetAsync(h->tail_zw, 0, (uint64_t)h->tail_cap * h->tail_cap * 4, h->stream));
+                HIPCHK(h, hipMemset2DAsync(h->lay.la + no, (size_t)h->pstride * 4, 0, (size_t)(used - no) * 4, h->hwm,
+                                           h->stream));
+            if (h->lay.tail_zw && h->tail_dirty)
+                HIPCHK(h, hipMemsetAsync(h->lay.tail_zw, 0, (uint64_t)h->lay.tail_cap() * h->lay.tail_cap() * 4, h->stream));
             h->tail_dirty = false;
         } else {
-            HIPCHK(h, hipMemsetAsync(h->la, 0, h->hwm * h->pstride * 4, h->stream));
+            HIPCHK(h, hipMemsetAsync(h->lay.la, 0, h->hwm * h->pstride * 4, h->stream));
         }
-        HIPCHK(h, lx::launch_fill_u32(h->first_child, h->hwm, LX_NONE, h->stream));
+        HIPCHK(h, lx::launch_fill_u32(h->lay.first_child, h->hwm, LX_NONE, h->stream));
         h->hwm = 0;
     }
     if (h->sharded()) {
@@ -1987,21 +1803,20 @@ int lx_reset(lx_index *h, uint32_t nv, const uint32_t *w) {
         h->nloc = norig;
         std::vector<uint32_t> wl(h->pstride, 0);
         for (uint32_t c = h->own_lo; c < h->own_hi; c++) wl[c - h->own_lo] = w[c];
-        HIPCHK(h, hipMemcpyAsync(h->wloc, wl.data(), (uint64_t)h->pstride * 4, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, lx::launch_fill_u32(h->cmap, h->cmap_cap, LX_NONE, h->stream));
-        HIPCHK(h, hipMemcpyAsync(h->cmap, h->h_cmap.data(), nv * 4ull, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->lay.wloc, wl.data(), (uint64_t)h->pstride * 4, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, lx::launch_fill_u32(h->lay.cmap, h->lay.cmap.cap(), LX_NONE, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->lay.cmap, h->h_cmap.data(), nv * 4ull, hipMemcpyHostToDevice, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
     }
-    if (h->first_root) (void)hipFree(h->first_root);
-    HIPCHK(h, dalloc(&h->first_root, nv));
-    HIPCHK(h, lx::launch_fill_u32(h->first_root, nv, LX_NONE, h->stream));
+    HIPCHK(h, h->lay.first_root.renew(nv));
+    HIPCHK(h, lx::launch_fill_u32(h->lay.first_root, nv, LX_NONE, h->stream));
     std::vector<uint32_t> ones(nv, 1), idx(nv), wp(h->stride, 0);
     for (uint32_t i = 0; i < nv; i++) idx[i] = i;
     for (uint32_t i = h->own_lo; i < h->own_hi; i++) wp[i] = w[i];
-    HIPCHK(h, hipMemsetAsync(h->branch_len, 0, (uint64_t)h->stride * 4, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->branch_first, ones.data(), nv * 4, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->branch_creator, idx.data(), nv * 4, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->wpad, wp.data(), (uint64_t)h->stride * 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemsetAsync(h->lay.branch_len, 0, (uint64_t)h->stride * 4, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->lay.branch_first, ones.data(), nv * 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->lay.branch_creator, idx.data(), nv * 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->lay.wpad, wp.data(), (uint64_t)h->stride * 4, hipMemcpyHostToDevice, h->stream));
     h->n_events = h->n_flushed = 0;
     h->rs_state = 0;
     h->pcols_used = h->sharded() ? norig : nv;
@@ -2074,7 +1889,7 @@ int lx_add_batch(lx_index *h, uint32_t n, const uint32_t *creator, const uint32_
     h->st_used[slot] = true;
     uint64_t start = h->n_events;
     if ((rc = add_batch_dev(h, n, dimg, dimg + a4, dimg + 2 * a4, dimg + 2 * a4 + o4, err_index))) return rc;
-    if (out_branch) HIPCHK(h, hipMemcpy(out_branch, h->ev_branch + start, n * 4ull, hipMemcpyDeviceToHost));
+    if (out_branch) HIPCHK(h, hipMemcpy(out_branch, h->lay.ev_branch + start, n * 4ull, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -2131,11 +1946,12 @@ int lx_drop_not_flushed(lx_index *h) {
         int rc;
         if ((rc = flush_pending(h))) return rc;
         HIPCHK(h, lx::launch_unfill(unfill_args(h), h->stream));
-        HIPCHK(h, lx::launch_zero_rows(h->hb, h->la, h->pstride, (uint32_t)h->n_flushed, (uint32_t)h->n_events, h->stream));
+        HIPCHK(h, lx::launch_zero_rows(h->lay.hb, h->lay.la, h->pstride, (uint32_t)h->n_flushed, (uint32_t)h->n_events,
+                                       h->stream));
         // re-added events may land on rows this epoch has not used yet (stale from an
         // earlier epoch) with seqs the tail table already counts as done: start over
-        if (h->tail_zw && h->tail_dirty) {
-            HIPCHK(h, hipMemsetAsync(h->tail_zw, 0, (uint64_t)h->tail_cap * h->tail_cap * 4, h->stream));
+        if (h->lay.tail_zw && h->tail_dirty) {
+            HIPCHK(h, hipMemsetAsync(h->lay.tail_zw, 0, (uint64_t)h->lay.tail_cap() * h->lay.tail_cap() * 4, h->stream));
             h->tail_dirty = false;
         }
     }
@@ -2165,7 +1981,7 @@ int lx_drop_not_flushed(lx_index *h) {
             for (uint32_t b = h->B; b < h->h_cmap.size(); b++)
                 if (h->h_cmap[b] != LX_NONE) h->nloc--;
             h->h_cmap.resize(h->B);
-            HIPCHK(h, lx::launch_fill_u32(h->cmap + h->B, h->cmap_cap - h->B, LX_NONE, h->stream));
+            HIPCHK(h, lx::launch_fill_u32(h->lay.cmap + h->B, h->lay.cmap.cap() - h->B, LX_NONE, h->stream));
         }
         return rebuild_columns(h);
     }
@@ -2190,21 +2006,22 @@ int lx_writeback_prepare(lx_index *h, lx_writeback *out) {
     hipStream_t s = h->stream;
     uint32_t n_la = 0;
     if (N > lo) {
-        HIPCHK(h, hipMemsetAsync(h->wb_flag, 0, N * 4ull, s));
-        HIPCHK(h, lx::launch_dirty_la(unfill_args(h), h->wb_flag, s));
-        HIPCHK(h, lx::launch_compact(h->wb_flag, h->wb_pos, N, h->wb_tmp, h->wb_tmp_bytes, h->wb_la_rows, s));
-        HIPCHK(h, hipMemcpyAsync(&n_la, h->wb_pos + (N - 1), 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(h, lx::launch_iota(h->wb_hb_rows, lo, N - lo, s));
+        HIPCHK(h, hipMemsetAsync(h->lay.wb_flag, 0, N * 4ull, s));
+        HIPCHK(h, lx::launch_dirty_la(unfill_args(h), h->lay.wb_flag, s));
+        HIPCHK(h, lx::launch_compact(h->lay.wb_flag, h->lay.wb_pos, N, h->lay.wb_tmp, h->lay.wb_tmp.cap(),
+                                     h->lay.wb_la_rows, s));
+        HIPCHK(h, hipMemcpyAsync(&n_la, h->lay.wb_pos + (N - 1), 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(h, lx::launch_iota(h->lay.wb_hb_rows, lo, N - lo, s));
         HIPCHK(h, hipStreamSynchronize(s));
     }
     // byte offsets of both row sets (wb_len is scratch, reused in stream order)
-    HIPCHK(h, lx::launch_row_offsets(rows_args(h, 0, h->wb_la_rows, n_la), h->wb_len, h->wb_la_off, h->wb_tmp,
-                                     h->wb_tmp_bytes, s));
-    HIPCHK(h, lx::launch_row_offsets(rows_args(h, 1, h->wb_hb_rows, N - lo), h->wb_len, h->wb_hb_off, h->wb_tmp,
-                                     h->wb_tmp_bytes, s));
+    HIPCHK(h, lx::launch_row_offsets(rows_args(h, 0, h->lay.wb_la_rows, n_la), h->lay.wb_len, h->lay.wb_la_off,
+                                     h->lay.wb_tmp, h->lay.wb_tmp.cap(), s));
+    HIPCHK(h, lx::launch_row_offsets(rows_args(h, 1, h->lay.wb_hb_rows, N - lo), h->lay.wb_len, h->lay.wb_hb_off,
+                                     h->lay.wb_tmp, h->lay.wb_tmp.cap(), s));
     uint64_t tot[2] = {0, 0};
-    HIPCHK(h, hipMemcpyAsync(&tot[0], h->wb_la_off + n_la, 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipMemcpyAsync(&tot[1], h->wb_hb_off + (N - lo), 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(&tot[0], h->lay.wb_la_off + n_la, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(&tot[1], h->lay.wb_hb_off + (N - lo), 8, hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipStreamSynchronize(s));
     if ((rc = branches_info_rlp(h, &h->wb_bi))) return rc;
     lx_writeback w{};
@@ -2228,15 +2045,17 @@ int lx_writeback_fetch(lx_index *h, uint64_t *hb_off, uint8_t *hb_bytes, uint32_
     const lx_writeback &w = h->wb;
     const uint32_t n = (uint32_t)w.n_events, m = (uint32_t)w.n_la_rows;
     int rc;
-    if ((hb_off || hb_bytes) && (rc = rows_to_host(h, 1, h->wb_hb_rows, h->wb_hb_off, n, hb_off, hb_bytes))) return rc;
+    if ((hb_off || hb_bytes) && (rc = rows_to_host(h, 1, h->lay.wb_hb_rows, h->lay.wb_hb_off, n, hb_off,
+                                                   hb_bytes))) return rc;
     if (la_ev && m) {
-        HIPCHK(h, hipMemcpyAsync(la_ev, h->wb_la_rows, m * 4ull, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(la_ev, h->lay.wb_la_rows, m * 4ull, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
     }
-    if ((la_off || la_bytes) && (rc = rows_to_host(h, 0, h->wb_la_rows, h->wb_la_off, m, la_off, la_bytes))) return rc;
+    if ((la_off || la_bytes) && (rc = rows_to_host(h, 0, h->lay.wb_la_rows, h->lay.wb_la_off, m, la_off,
+                                                   la_bytes))) return rc;
     if (branch_be && n) {
         std::vector<uint32_t> br(n);
-        HIPCHK(h, hipMemcpyAsync(br.data(), h->ev_branch + w.first_event, n * 4ull, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(br.data(), h->lay.ev_branch + w.first_event, n * 4ull, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
         for (uint32_t i = 0; i < n; i++)
             for (int k = 0; k < 4; k++) branch_be[4 * i + k] = (uint8_t)(br[i] >> (24 - 8 * k));
@@ -2316,18 +2135,13 @@ int lx_fc_shard_undecided_dev(lx_index *h, uint64_t n, const uint64_t *mask, con
     *m = 0;
     if (!n) return 0;
     HIPCHK(h, set_dev(h->device));
-    if (n > h->fcs_cap) {
+    if (n > h->fcs_flag.cap()) {
         (void)hipStreamSynchronize(h->stream);
-        for (void *q : {(void *)h->fcs_flag, (void *)h->fcs_pos, h->fcs_tmp})
-            if (q) (void)hipFree(q);
-        h->fcs_flag = h->fcs_pos = nullptr;
-        h->fcs_tmp = nullptr;
-        h->fcs_cap = 0;
-        HIPCHK(h, lxi::dalloc(&h->fcs_flag, n));
-        HIPCHK(h, lxi::dalloc(&h->fcs_pos, n));
+        h->fcs_flag.reset();   // (the capacity the check above reads: set last)
+        HIPCHK(h, h->fcs_pos.renew(n));
         HIPCHK(h, lx::fcs_scan_bytes(n, &h->fcs_tmp_bytes));
-        HIPCHK(h, hipMalloc(&h->fcs_tmp, std::max<size_t>(h->fcs_tmp_bytes, 16)));
-        h->fcs_cap = n;
+        HIPCHK(h, h->fcs_tmp.renew(std::max<size_t>(h->fcs_tmp_bytes, 16)));
+        HIPCHK(h, h->fcs_flag.renew(n));
     }
     HIPCHK(h, lx::launch_fcs_undecided(reinterpret_cast<const unsigned long long *>(mask), n, a, b, partial, h->fcs_flag,
                                        h->fcs_pos, h->fcs_tmp, h->fcs_tmp_bytes, idx, a_out, b_out, p_out, h->stream));
@@ -2398,23 +2212,20 @@ int lx_forkless_cause_batch(lx_index *h, uint64_t n, const uint32_t *a, const ui
             if (out[i] > 1) return h->fail(LX_ERR_ARG, "ForklessCause on an unknown event");   // forkless_cause.go:43-61
         return 0;
     }
-    if (n > h->q_cap) {
+    if (n > h->lay.q_a.cap()) {
         uint64_t cap = std::max<uint64_t>(n, 4096);
-        if (h->q_a) (void)hipFree(h->q_a);
-        if (h->q_b) (void)hipFree(h->q_b);
-        if (h->q_out) (void)hipFree(h->q_out);
-        HIPCHK(h, dalloc(&h->q_a, cap));
-        HIPCHK(h, dalloc(&h->q_b, cap));
-        HIPCHK(h, dalloc(&h->q_out, cap));
-        h->q_cap = cap;
+        h->lay.q_a.reset();   // (the capacity the check above reads: set last)
+        HIPCHK(h, h->lay.q_b.renew(cap));
+        HIPCHK(h, h->lay.q_out.renew(cap));
+        HIPCHK(h, h->lay.q_a.renew(cap));
     }
     HIPCHK(h, hipMemsetAsync(h->status + 1, 0, 4, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->q_a, a, n * 4, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->q_b, b, n * 4, hipMemcpyHostToDevice, h->stream));
-    int rc = lx_forkless_cause_batch_dev(h, n, h->q_a, h->q_b, h->q_out, nullptr);
+    HIPCHK(h, hipMemcpyAsync(h->lay.q_a, a, n * 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->lay.q_b, b, n * 4, hipMemcpyHostToDevice, h->stream));
+    int rc = lx_forkless_cause_batch_dev(h, n, h->lay.q_a, h->lay.q_b, h->lay.q_out, nullptr);
     if (rc) return rc;
     uint32_t bad = 0;
-    HIPCHK(h, hipMemcpyAsync(out, h->q_out, n, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(out, h->lay.q_out, n, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipMemcpyAsync(&bad, h->status + 1, 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (bad) return h->fail(LX_ERR_ARG, "ForklessCause on an unknown event");   // forkless_cause.go:43-61 (crit)
@@ -2431,7 +2242,7 @@ int lx_get_event_branch_id(lx_index *h, uint32_t ev, uint32_t *out) {
     }
     HIPCHK(h, set_dev(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    return read_u32(h, h->ev_branch + ev, out);
+    return read_u32(h, h->lay.ev_branch + ev, out);
 }
 
 }  // extern "C"
@@ -2466,8 +2277,8 @@ GetSrvArgs srv_args_of(const lx_index *h, const GetArgs &a) {
     // getter_host_check, refuses such events before any request is posted),
     // so that an Add between two getters does not relaunch it
     if (!h->rowseg()) s.g.row_hi = (uint32_t)std::min<uint64_t>(h->n_cap, 0xFFFFFFFFull);
-    s.hb = h->hb;
-    s.la = h->la;
+    s.hb = h->lay.hb;
+    s.la = h->lay.la;
     s.req = h->srv_dev;
     s.exited = reinterpret_cast<uint32_t *>(h->srv_dev + 1);
     return s;
@@ -2494,7 +2305,7 @@ int srv_launch(lx_index *h, const GetArgs &a, uint32_t seen0) {
 // the request word between requests
 void srv_stop(lx_index *h) {
     if (!h || !h->srv_live) return;
-    reinterpret_cast<volatile uint64_t *>(h->srv_host)[0] = kGetSrvStop;
+    reinterpret_cast<volatile uint64_t *>(h->srv_host.get())[0] = kGetSrvStop;
     (void)hipStreamSynchronize(h->srv_stream);
     h->srv_live = false;
 }
@@ -2519,26 +2330,26 @@ int srv_post(lx_index *h, const GetArgs &a, bool *posted) {
     if (!h->srv_host) {
         // what the server needs; without any of it the getters launch as before
         int lo = 0, hi = 0, khz = 0;
-        void *p = nullptr, *d = nullptr;
+        decltype(h->srv_host) p;
+        void *d = nullptr;
         bool ok = hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, h->device) == hipSuccess && khz >= 1000 &&
                   hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess;
         if (ok && !h->srv_stream) ok = hipStreamCreateWithPriority(&h->srv_stream, hipStreamNonBlocking, hi) == hipSuccess;
-        if (ok) ok = hipHostMalloc(&p, 64, hipHostMallocMapped) == hipSuccess;
+        if (ok) ok = p.renew(8) == hipSuccess;
         if (ok) ok = hipHostGetDevicePointer(&d, p, 0) == hipSuccess;
         if (!ok) {
-            if (p) (void)hipHostFree(p);
             (void)hipGetLastError();
             h->srv_opt = 0;
             return 0;
         }
         memset(p, 0, 64);
         h->srv_ticks_us = (uint64_t)khz / 1000;
-        h->srv_host = static_cast<uint64_t *>(p);
+        h->srv_host = std::move(p);
         h->srv_dev = static_cast<uint64_t *>(d);
     }
     volatile uint64_t *req = h->srv_host;
     const GetSrvArgs want = srv_args_of(h, a);
-    if (h->srv_live && (uint32_t)reinterpret_cast<volatile uint64_t *>(h->srv_host)[1] == h->srv_gen) {
+    if (h->srv_live && (uint32_t)reinterpret_cast<volatile uint64_t *>(h->srv_host.get())[1] == h->srv_gen) {
         (void)hipStreamSynchronize(h->srv_stream);   // it left (idle or deadline): its launch has ended
         h->srv_live = false;
     }
@@ -2559,7 +2370,7 @@ int get_rows(lx_index *h, uint32_t mode, uint32_t n, const uint32_t *ev, uint8_t
     if ((rc = ensure_qp(h, head + n * sl, &hp, &dp))) return rc;
     if (n > 1) memcpy(hp, ev, n * 4ull);
     GetArgs a{};
-    a.plane = mode == 1 ? h->la : h->hb;
+    a.plane = mode == 1 ? h->lay.la : h->lay.hb;
     a.stride = h->stride;
     // one row: the event travels in the arguments (no read of host memory)
     a.ev = n > 1 ? reinterpret_cast<const uint32_t *>(dp) : nullptr;
@@ -2569,12 +2380,12 @@ int get_rows(lx_index *h, uint32_t mode, uint32_t n, const uint32_t *ev, uint8_t
     a.V = h->V;
     a.mode = mode;
     a.forks = h->B > h->V ? 1u : 0u;
-    a.ev_bbefore = h->ev_bbefore;
-    a.ev_branch = h->ev_branch;
-    a.branch_first = h->branch_first;
-    a.cheat_of = h->cheat_of;
-    a.cheat_off = h->cheat_off;
-    a.cheat_br = h->cheat_br;
+    a.ev_bbefore = h->lay.ev_bbefore;
+    a.ev_branch = h->lay.ev_branch;
+    a.branch_first = h->lay.branch_first;
+    a.cheat_of = h->lay.cheat_of;
+    a.cheat_off = h->lay.cheat_off;
+    a.cheat_br = h->lay.cheat_br;
     a.len = reinterpret_cast<uint32_t *>(dp + 4ull * n);
     a.out = dp + head;
     a.slot = sl;
@@ -2602,8 +2413,8 @@ int get_rows(lx_index *h, uint32_t mode, uint32_t n, const uint32_t *ev, uint8_t
         bool relaunched = false;
         for (uint32_t k = 0; *done != a.tag; k++) {
             if ((k & 63) != 63) continue;
-            if (posted && !relaunched && (uint32_t)reinterpret_cast<volatile uint64_t *>(h->srv_host)[1] == h->srv_gen &&
-                *done != a.tag) {
+            if (posted && !relaunched &&
+                (uint32_t)reinterpret_cast<volatile uint64_t *>(h->srv_host.get())[1] == h->srv_gen && *done != a.tag) {
                 // the server left (idle or its deadline) before it saw the request
                 h->srv_live = false;
                 if ((rc = srv_launch(h, a, a.tag == 1 ? kGetSrvStop - 1 : a.tag - 1))) return rc;
@@ -2759,7 +2570,7 @@ int lx_get_rows_dev(lx_index *h, uint32_t mode, uint32_t n, const uint32_t *ev_d
     HIPCHK(h, set_dev(h->device));
     if (!n) return 0;
     GetArgs a{};
-    a.plane = mode == 1 ? h->la : h->hb;
+    a.plane = mode == 1 ? h->lay.la : h->lay.hb;
     a.stride = h->pstride;
     a.ev = ev_dev;
     a.n = n;
@@ -2767,12 +2578,12 @@ int lx_get_rows_dev(lx_index *h, uint32_t mode, uint32_t n, const uint32_t *ev_d
     a.V = h->V;
     a.mode = mode;
     a.forks = h->B > h->V ? 1u : 0u;
-    a.ev_bbefore = h->ev_bbefore;
-    a.ev_branch = h->ev_branch;
-    a.branch_first = h->branch_first;
-    a.cheat_of = h->cheat_of;
-    a.cheat_off = h->cheat_off;
-    a.cheat_br = h->cheat_br;
+    a.ev_bbefore = h->lay.ev_bbefore;
+    a.ev_branch = h->lay.ev_branch;
+    a.branch_first = h->lay.branch_first;
+    a.cheat_of = h->lay.cheat_of;
+    a.cheat_off = h->lay.cheat_off;
+    a.cheat_br = h->lay.cheat_br;
     a.len = len_dev;
     a.out = out_dev;
     a.slot = slot_bytes;
@@ -2781,7 +2592,7 @@ int lx_get_rows_dev(lx_index *h, uint32_t mode, uint32_t n, const uint32_t *ev_d
     if (h->sharded()) {
         // this shard's branches only, the rest of every slot zero: the shards'
         // slots sum word by word to the whole row (lx_shard_get_rows)
-        a.cmap = h->cmap;
+        a.cmap = h->lay.cmap;
         HIPCHK(h, hipMemsetAsync(out_dev, 0, (uint64_t)n * slot_bytes, h->stream));
     }
     HIPCHK(h, lx::launch_get_rows(a, h->stream));
@@ -2837,7 +2648,7 @@ int lx_shard_block(lx_index *h, uint32_t src, uint32_t dst, uint64_t *elems) {
     HIPCHK(h, set_dev(h->device));
     int rc;
     if ((rc = h->sx_active ? ensure_shard_cols(h) : ensure_shard_rows(h))) return rc;
-    const uint64_t nrows = h->sx_active ? h->sx_roff[src + 1] - h->sx_roff[src] : h->sc_nrows[src];
+    const uint64_t nrows = h->sx_active ? h->sx_roff[src + 1] - h->sx_roff[src] : h->lay.sc_nrows[src];
     *elems = nrows * (h->sc_col_off[dst + 1] - h->sc_col_off[dst]);
     return 0;
 }
@@ -2853,35 +2664,35 @@ static int la_xfer(lx_index *h, uint32_t rows_of, uint32_t cols_of, uint32_t *bu
     if ((rc = h->sx_active ? ensure_shard_cols(h) : ensure_shard_rows(h))) return rc;
     const uint32_t c0 = h->sc_col_off[cols_of], c1 = h->sc_col_off[cols_of + 1];
     XferArgs x{};
-    x.lap = h->lap;
+    x.lap = h->lay.lap;
     x.lap_stride = h->stride;
     x.s_cap = h->s_cap;
-    x.la = h->la;
+    x.la = h->lay.la;
     x.pstride = h->pstride;
-    x.cmap = h->cmap;
-    x.ev_branch = h->ev_branch;
-    x.ev_seq = h->ev_seq;
-    x.branch_first = h->branch_first;
+    x.cmap = h->lay.cmap;
+    x.ev_branch = h->lay.ev_branch;
+    x.ev_seq = h->lay.ev_seq;
+    x.branch_first = h->lay.branch_first;
     // the dirty rows of an incremental exchange (lx_shard_dirty_set), else every row
-    x.rows = h->sx_active ? h->sx_rows + h->sx_roff[rows_of] : h->sc_rows[rows_of];
-    x.nrows = h->sx_active ? (uint32_t)(h->sx_roff[rows_of + 1] - h->sx_roff[rows_of]) : h->sc_nrows[rows_of];
-    x.cols = h->sc_cols + c0;
+    x.rows = h->sx_active ? h->lay.sx_rows + h->sx_roff[rows_of] : h->lay.sc_rows[rows_of];
+    x.nrows = h->sx_active ? (uint32_t)(h->sx_roff[rows_of + 1] - h->sx_roff[rows_of]) : h->lay.sc_nrows[rows_of];
+    x.cols = h->lay.sc_cols + c0;
     x.ncols = c1 - c0;
     x.buf = buf;
     x.mode = mode;
     x.wire = wire ? wire : shard_wire_bytes(h);
     const bool check = mode == 3 || (mode == 0 && x.wire == 1);
     if (check) {
-        if (!h->wire_flag) HIPCHK(h, dalloc(&h->wire_flag, 1));
-        HIPCHK(h, hipMemsetAsync(h->wire_flag, 0, 4, h->stream));
-        x.flag = h->wire_flag;
-        if (mode == 3) x.buf = h->wire_flag;
+        HIPCHK(h, h->lay.wire_flag.grow(1));
+        HIPCHK(h, hipMemsetAsync(h->lay.wire_flag, 0, 4, h->stream));
+        x.flag = h->lay.wire_flag;
+        if (mode == 3) x.buf = h->lay.wire_flag;
     }
     HIPCHK(h, lx::launch_la_xfer(x, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (check) {
         uint32_t bad = 0;
-        HIPCHK(h, hipMemcpy(&bad, h->wire_flag, 4, hipMemcpyDeviceToHost));
+        HIPCHK(h, hipMemcpy(&bad, h->lay.wire_flag, 4, hipMemcpyDeviceToHost));
         if (mode == 3) return bad ? 1 : 0;
         if (bad) return h->fail(LX_ERR_WIRE, "LowestAfter block to shard %u does not fit the 1-byte wire", cols_of);
     }
@@ -2954,15 +2765,11 @@ int lx_shard_dirty(lx_index *h, uint32_t nb, uint32_t *dmin) {
     if ((rc = flush_pending(h)) || (rc = ensure_shard_cols(h))) return rc;
     for (uint32_t b = 0; b < nb; b++) dmin[b] = LX_NONE;
     const uint32_t c0 = h->sc_col_off[h->shard_rank], c1 = h->sc_col_off[h->shard_rank + 1];
-    if (h->sx_cap < h->stride || !h->sx_len) {
-        for (void *p : {(void *)h->sx_len, (void *)h->sx_dmin})
-            if (p) (void)hipFree(p);
-        h->sx_len = h->sx_dmin = nullptr;
-        h->sx_cap = 0;
-        HIPCHK(h, dalloc(&h->sx_len, h->stride));
-        HIPCHK(h, dalloc(&h->sx_dmin, h->stride));
-        HIPCHK(h, hipMemsetAsync(h->sx_len, 0, (uint64_t)h->stride * 4, h->stream));
-        h->sx_cap = h->stride;
+    if (h->lay.sx_len.cap() < h->stride || !h->lay.sx_len) {
+        h->lay.sx_len.reset();   // (the capacity the check above reads: set last)
+        HIPCHK(h, h->lay.sx_dmin.renew(h->stride));
+        HIPCHK(h, h->lay.sx_len.renew(h->stride));
+        HIPCHK(h, hipMemsetAsync(h->lay.sx_len, 0, (uint64_t)h->stride * 4, h->stream));
         h->sx_full = true;
     }
     if (h->sx_full) {
@@ -2972,10 +2779,11 @@ int lx_shard_dirty(lx_index *h, uint32_t nb, uint32_t *dmin) {
         return 0;
     }
     if (!h->B || c1 == c0) return 0;
-    HIPCHK(h, lx::launch_fill_u32(h->sx_dmin, h->B, LX_NONE, h->stream));
-    HIPCHK(h, lx::launch_shard_dmin(h->hb, h->pstride, h->cmap, h->branch_len, h->brow, h->s_cap, h->branch_first,
-                                    h->sx_len, h->B, h->sc_cols + c0, c1 - c0, h->sx_dmin, h->stream));
-    HIPCHK(h, hipMemcpyAsync(dmin, h->sx_dmin, 4ull * h->B, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, lx::launch_fill_u32(h->lay.sx_dmin, h->B, LX_NONE, h->stream));
+    HIPCHK(h, lx::launch_shard_dmin(h->lay.hb, h->pstride, h->lay.cmap, h->lay.branch_len, h->lay.brow, h->s_cap,
+                                    h->lay.branch_first,
+                                    h->lay.sx_len, h->B, h->lay.sc_cols + c0, c1 - c0, h->lay.sx_dmin, h->stream));
+    HIPCHK(h, hipMemcpyAsync(dmin, h->lay.sx_dmin, 4ull * h->B, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return 0;
 }
@@ -2989,7 +2797,7 @@ int lx_shard_dirty_set(lx_index *h, uint32_t nb, const uint32_t *dmin) {
     if ((rc = ensure_shard_cols(h))) return rc;
     const uint32_t B = h->B, G = h->shard_count;
     std::vector<uint32_t> len(B);
-    if (B) HIPCHK(h, hipMemcpyAsync(len.data(), h->branch_len, 4ull * B, hipMemcpyDeviceToHost, h->stream));
+    if (B) HIPCHK(h, hipMemcpyAsync(len.data(), h->lay.branch_len, 4ull * B, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     // per shard, its branches in order: {branch, first dirty index, row offset}
     std::vector<uint32_t> meta;
@@ -3012,13 +2820,13 @@ int lx_shard_dirty_set(lx_index *h, uint32_t nb, const uint32_t *dmin) {
     }
     h->sx_roff[G] = total;
     if (total > 0xFFFFFFFFull) return h->fail(LX_ERR_ARG, "too many dirty rows");
-    if ((rc = grow_scratch(h, &h->sx_rows, &h->sx_rows_cap, total + 1)) ||
-        (rc = grow_scratch(h, &h->sx_meta, &h->sx_meta_cap, (uint64_t)meta.size() + 4)))
+    if ((rc = grow_scratch(h, h->lay.sx_rows, total + 1)) ||
+        (rc = grow_scratch(h, h->lay.sx_meta, (uint64_t)meta.size() + 4)))
         return rc;
     if (!meta.empty()) {
-        HIPCHK(h, hipMemcpyAsync(h->sx_meta, meta.data(), meta.size() * 4, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, lx::launch_shard_dirty_rows(h->brow, h->s_cap, h->sx_meta, (uint32_t)(meta.size() / 4), h->sx_rows,
-                                              h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->lay.sx_meta, meta.data(), meta.size() * 4, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, lx::launch_shard_dirty_rows(h->lay.brow, h->s_cap, h->lay.sx_meta, (uint32_t)(meta.size() / 4),
+                                              h->lay.sx_rows, h->stream));
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));   // `meta` is a host temporary
     h->sx_active = true;
@@ -3029,8 +2837,8 @@ int lx_shard_dirty_commit(lx_index *h) {
     if (!h) return LX_ERR_ARG;
     if (!h->sharded()) return h->fail(LX_ERR_STATE, "the incremental exchange needs a column-sharded handle");
     HIPCHK(h, set_dev(h->device));
-    if (h->sx_len && h->B) {
-        HIPCHK(h, hipMemcpyAsync(h->sx_len, h->branch_len, 4ull * h->B, hipMemcpyDeviceToDevice, h->stream));
+    if (h->lay.sx_len && h->B) {
+        HIPCHK(h, hipMemcpyAsync(h->lay.sx_len, h->lay.branch_len, 4ull * h->B, hipMemcpyDeviceToDevice, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
         h->sx_full = false;
     }
@@ -3057,8 +2865,8 @@ int lx_device_planes(lx_index *h, void **hb, void **la, uint32_t *stride, void *
         const int rc = flush_pending(h);   // the caller reads the planes in stream order after this
         if (rc) return rc;
     }
-    if (hb) *hb = h->hb;
-    if (la) *la = h->la;
+    if (hb) *hb = h->lay.hb;
+    if (la) *la = h->lay.la;
     if (stride) *stride = h->pstride;
     if (stream) *stream = h->stream;
     return 0;
@@ -3066,18 +2874,19 @@ int lx_device_planes(lx_index *h, void **hb, void **la, uint32_t *stride, void *
 
 int lx_device_bytes(const lx_index *h, uint64_t out[4]) {
     if (!h || !out) return LX_ERR_ARG;
+    const Layout &l = h->lay;
     const uint64_t ps = h->pstride;
-    uint64_t planes = h->rs_hb_mem ? 2 * h->rs_mem_rows * ps * 4 : (h->hb ? 2 * h->n_cap * ps * 4 : 0);
-    if (h->lap) planes += (uint64_t)h->pstride * h->s_cap * h->stride * 4;
-    const uint64_t recv = 4 * (h->rs_rhb_cap + h->rs_rla_cap);
+    uint64_t planes = h->rowseg() ? 2 * l.rs_mem_rows * ps * 4 : (l.hb ? 2 * h->n_cap * ps * 4 : 0);
+    if (l.lap) planes += (uint64_t)h->pstride * h->s_cap * h->stride * 4;
+    const uint64_t recv = 4 * (l.rs_rhb.cap() + l.rs_rla.cap());
     uint64_t per_ev = 6 * 4 * h->n_cap;   // creator, seq, branch, bbefore, sp, first_child
-    for (uint64_t c : {h->seg_mf_cap, h->seg_plist_cap, h->seg_elist_cap, h->rs_need_cap, h->rs_hslot_cap,
-                       h->rs_lslot_cap, h->rs_stamp_cap, h->wb_cap})
-        per_ev += 4 * c;
-    uint64_t other = 4 * ((uint64_t)h->stride * h->s_cap + 5ull * h->stride + h->tail_cap * (uint64_t)h->tail_cap * 2);
-    other += 4 * (8 * h->batch_cap + h->par_cap + 2 * h->q_cap) + h->q_cap + 16 * h->batch_cap;
-    other += 4 * (h->rs_req_cap + h->rs_ids_cap + h->rs_out_cap + h->rs_send_cap + h->rsq_scratch_cap + h->rsq_list_cap) +
-             h->rsq_tmp_bytes + h->scan_bytes;
+    for (const DU32 *b : {&l.seg_mf, &l.seg_plist, &l.seg_elist, &l.rs_need, &l.rs_hslot, &l.rs_lslot, &l.rs_stamp,
+                          &l.wb_flag})
+        per_ev += b->bytes();
+    uint64_t other = 4 * ((uint64_t)h->stride * h->s_cap + 5ull * h->stride + l.tail_cap() * (uint64_t)l.tail_cap() * 2);
+    other += 4 * (8 * l.batch_cap + l.b_par.cap() + 2 * l.q_a.cap()) + l.q_a.cap() + 16 * l.batch_cap;
+    for (const DU32 *b : {&l.rs_req, &l.rs_ids, &l.rs_out, &l.rs_send, &l.rsq_scratch, &l.rsq_list}) other += b->bytes();
+    other += l.rsq_tmp.bytes() + l.scan_tmp.bytes();
     out[0] = planes;
     out[1] = recv;
     out[2] = per_ev;
@@ -3273,34 +3082,25 @@ int lx_load_rows(lx_index *h, uint32_t n, const uint32_t *creator, const uint32_
     std::vector<uint32_t> sp(n);
     for (uint32_t i = 0; i < n; i++)
         sp[i] = seq[i] > 1 ? par[poff[i]] : LX_NONE;
-    HIPCHK(h, hipMemcpyAsync(h->ev_creator + bs, h->hm_creator.data() + bs, n * 4ull, hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipMemcpyAsync(h->ev_seq + bs, h->hm_seq.data() + bs, n * 4ull, hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipMemcpyAsync(h->ev_branch + bs, h->hm_branch.data() + bs, n * 4ull, hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipMemcpyAsync(h->ev_bbefore + bs, h->hm_bbefore.data() + bs, n * 4ull, hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipMemcpyAsync(h->ev_sp + bs, sp.data(), n * 4ull, hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipMemcpyAsync(h->branch_first, h->ld_first.data(), h->ld_B * 4ull, hipMemcpyHostToDevice, st));
+    HIPCHK(h, hipMemcpyAsync(h->lay.ev_creator + bs, h->hm_creator.data() + bs, n * 4ull, hipMemcpyHostToDevice, st));
+    HIPCHK(h, hipMemcpyAsync(h->lay.ev_seq + bs, h->hm_seq.data() + bs, n * 4ull, hipMemcpyHostToDevice, st));
+    HIPCHK(h, hipMemcpyAsync(h->lay.ev_branch + bs, h->hm_branch.data() + bs, n * 4ull, hipMemcpyHostToDevice, st));
+    HIPCHK(h, hipMemcpyAsync(h->lay.ev_bbefore + bs, h->hm_bbefore.data() + bs, n * 4ull, hipMemcpyHostToDevice, st));
+    HIPCHK(h, hipMemcpyAsync(h->lay.ev_sp + bs, sp.data(), n * 4ull, hipMemcpyHostToDevice, st));
+    HIPCHK(h, hipMemcpyAsync(h->lay.branch_first, h->ld_first.data(), h->ld_B * 4ull, hipMemcpyHostToDevice, st));
     // the chunk's table bytes and offsets
     const uint64_t hb_n = hb_off[n] - hb_off[0], la_n = la_off[n] - la_off[0];
     const uint64_t o_hoff = (hb_n + la_n + 15) / 16 * 16, o_loff = o_hoff + 8ull * (n + 1);
     const uint64_t need = o_loff + 8ull * (n + 1);
-    if (need > h->ld_buf_cap) {
-        if (h->ld_buf) {
-            HIPCHK(h, hipStreamSynchronize(st));
-            (void)hipFree(h->ld_buf);
-        }
-        h->ld_buf = nullptr;
-        h->ld_buf_cap = 0;
-        HIPCHK(h, hipMalloc((void **)&h->ld_buf, need));
-        h->ld_buf_cap = need;
-    }
+    HIPCHK(h, h->ld_buf.grow(need, st, true));
     HIPCHK(h, hipMemcpyAsync(h->ld_buf, hb_bytes + hb_off[0], hb_n, hipMemcpyHostToDevice, st));
     HIPCHK(h, hipMemcpyAsync(h->ld_buf + hb_n, la_bytes + la_off[0], la_n, hipMemcpyHostToDevice, st));
     HIPCHK(h, hipMemcpyAsync(h->ld_buf + o_hoff, hb_off, 8ull * (n + 1), hipMemcpyHostToDevice, st));
     HIPCHK(h, hipMemcpyAsync(h->ld_buf + o_loff, la_off, 8ull * (n + 1), hipMemcpyHostToDevice, st));
     HIPCHK(h, hipMemsetAsync(h->status + 5, 0, 4, st));
     LoadArgs a{};
-    a.hb = h->hb;
-    a.la = h->la;
+    a.hb = h->lay.hb;
+    a.la = h->lay.la;
     a.stride = h->stride;
     a.bs = (uint32_t)bs;
     a.n = n;
@@ -3311,10 +3111,10 @@ int lx_load_rows(lx_index *h, uint32_t n, const uint32_t *creator, const uint32_
     a.la_base = la_off[0] - hb_n;   // la bytes follow the hb bytes in the staging buffer
     a.hb_bytes = h->ld_buf;
     a.la_bytes = h->ld_buf;
-    a.ev_branch = h->ev_branch;
-    a.ev_seq = h->ev_seq;
-    a.branch_first = h->branch_first;
-    a.brow = h->brow;
+    a.ev_branch = h->lay.ev_branch;
+    a.ev_seq = h->lay.ev_seq;
+    a.branch_first = h->lay.branch_first;
+    a.brow = h->lay.brow;
     a.s_cap = h->s_cap;
     a.bad = h->status + 5;
     HIPCHK(h, lx::launch_load_rows(a, st));
@@ -3390,11 +3190,11 @@ int lx_load_finish(lx_index *h, const uint8_t *bi_rlp, uint32_t bi_len) {
         }
     }
     hipStream_t st = h->stream;
-    HIPCHK(h, hipMemcpyAsync(h->branch_first, h->h_branch_first.data(), B * 4ull, hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipMemcpyAsync(h->branch_creator, cr.data(), B * 4ull, hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipMemcpyAsync(h->branch_len, blen.data(), B * 4ull, hipMemcpyHostToDevice, st));
-    if (N) HIPCHK(h, hipMemcpyAsync(h->first_child, fchild.data(), N * 4ull, hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipMemcpyAsync(h->first_root, froot.data(), V * 4ull, hipMemcpyHostToDevice, st));
+    HIPCHK(h, hipMemcpyAsync(h->lay.branch_first, h->h_branch_first.data(), B * 4ull, hipMemcpyHostToDevice, st));
+    HIPCHK(h, hipMemcpyAsync(h->lay.branch_creator, cr.data(), B * 4ull, hipMemcpyHostToDevice, st));
+    HIPCHK(h, hipMemcpyAsync(h->lay.branch_len, blen.data(), B * 4ull, hipMemcpyHostToDevice, st));
+    if (N) HIPCHK(h, hipMemcpyAsync(h->lay.first_child, fchild.data(), N * 4ull, hipMemcpyHostToDevice, st));
+    HIPCHK(h, hipMemcpyAsync(h->lay.first_root, froot.data(), V * 4ull, hipMemcpyHostToDevice, st));
     h->pcols_used = std::max(h->pcols_used, B);
     if ((rc = rebuild_columns(h))) return rc;   // syncs the stream
     if (N) {
@@ -3402,15 +3202,15 @@ int lx_load_finish(lx_index *h, const uint8_t *bi_rlp, uint32_t bi_len) {
         // below verify those); a marker anywhere else is corrupt
         std::vector<uint32_t> cheat_col(B, 0);
         for (uint32_t b = 0; b < B; b++) cheat_col[b] = by[cr[b]].size() > 1 ? 1u : 0u;
-        uint32_t *d_cc = nullptr;
-        HIPCHK(h, hipMalloc((void **)&d_cc, 4ull * B));
+        DU32 d_cc;
+        HIPCHK(h, d_cc.renew(B));
         HIPCHK(h, hipMemcpyAsync(d_cc, cheat_col.data(), 4ull * B, hipMemcpyHostToDevice, st));
         HIPCHK(h, hipMemsetAsync(h->status + 5, 0, 4, st));
-        HIPCHK(h, lx::launch_load_marks_ok(h->hb, h->stride, (uint32_t)N, B, d_cc, h->status + 5, st));
+        HIPCHK(h, lx::launch_load_marks_ok(h->lay.hb, h->stride, (uint32_t)N, B, d_cc, h->status + 5, st));
         uint32_t bad = 0;
         HIPCHK(h, hipMemcpyAsync(&bad, h->status + 5, 4, hipMemcpyDeviceToHost, st));
         HIPCHK(h, hipStreamSynchronize(st));
-        (void)hipFree(d_cc);
+        d_cc.reset();
         if (bad) return load_fail(h, "fork marker in a column of a creator with one branch");
     }
     if (B > V && h->n_cheat && N) {
@@ -3434,10 +3234,11 @@ int lx_load_finish(lx_index *h, const uint8_t *bi_rlp, uint32_t bi_len) {
         std::vector<uint32_t> cur(off.begin(), off.end() - 1);
         for (uint64_t e = 0; e < N; e++) perm[cur[lvl[e]]++] = (uint32_t)e;
         const uint64_t npar = h->ld_par.size();
-        uint8_t *scratch = nullptr;
+        DBytes d_scratch;
         const uint64_t o_perm = 4ull * ncc, o_off = o_perm + 4ull * N, o_poff = (o_off + 4ull * (L + 1) + 7) / 8 * 8,
                        o_par = o_poff + 8ull * (N + 1), o_lm = o_par + 4ull * std::max<uint64_t>(npar, 1);
-        HIPCHK(h, hipMalloc((void **)&scratch, o_lm + N * ncc));
+        HIPCHK(h, d_scratch.renew(o_lm + N * ncc));
+        uint8_t *scratch = d_scratch;
         HIPCHK(h, hipMemcpyAsync(scratch, cols.data(), 4ull * ncc, hipMemcpyHostToDevice, st));
         HIPCHK(h, hipMemcpyAsync(scratch + o_perm, perm.data(), 4ull * N, hipMemcpyHostToDevice, st));
         HIPCHK(h, hipMemcpyAsync(scratch + o_off, off.data(), 4ull * (L + 1), hipMemcpyHostToDevice, st));
@@ -3445,7 +3246,7 @@ int lx_load_finish(lx_index *h, const uint8_t *bi_rlp, uint32_t bi_len) {
         if (npar) HIPCHK(h, hipMemcpyAsync(scratch + o_par, h->ld_par.data(), 4ull * npar, hipMemcpyHostToDevice, st));
         HIPCHK(h, hipMemsetAsync(h->status + 5, 0, 4, st));
         LoadRawArgs r{};
-        r.hb = h->hb;
+        r.hb = h->lay.hb;
         r.stride = h->stride;
         r.cols = reinterpret_cast<const uint32_t *>(scratch);
         r.ncc = ncc;
@@ -3454,43 +3255,42 @@ int lx_load_finish(lx_index *h, const uint8_t *bi_rlp, uint32_t bi_len) {
         r.n_levels = L;
         r.poff = reinterpret_cast<const uint64_t *>(scratch + o_poff);
         r.par = reinterpret_cast<const uint32_t *>(scratch + o_par);
-        r.ev_branch = h->ev_branch;
-        r.ev_seq = h->ev_seq;
+        r.ev_branch = h->lay.ev_branch;
+        r.ev_seq = h->lay.ev_seq;
         r.lm = scratch + o_lm;
         r.bad = h->status + 5;
         HIPCHK(h, lx::launch_load_raw(r, st));
         MarkArgs m{};
-        m.hb = h->hb;
+        m.hb = h->lay.hb;
         m.stride = h->pstride;
         m.batch_start = 0;
         m.n = (uint32_t)N;
         m.V = V;
-        m.ev_branch = h->ev_branch;
-        m.ev_bbefore = h->ev_bbefore;
-        m.branch_first = h->branch_first;
+        m.ev_branch = h->lay.ev_branch;
+        m.ev_bbefore = h->lay.ev_bbefore;
+        m.branch_first = h->lay.branch_first;
         m.n_cheat = h->n_cheat;
-        m.cheat_off = h->cheat_off;
-        m.cheat_br = h->cheat_br;
+        m.cheat_off = h->lay.cheat_off;
+        m.cheat_br = h->lay.cheat_br;
         HIPCHK(h, lx::launch_marks(m, st));
         HIPCHK(h, lx::launch_load_check(r, (uint32_t)N, st));
         uint32_t bad = 0;
         HIPCHK(h, hipMemcpyAsync(&bad, h->status + 5, 4, hipMemcpyDeviceToHost, st));
         HIPCHK(h, hipStreamSynchronize(st));
-        (void)hipFree(scratch);
         if (bad) return load_fail(h, "fork markers / raw HighestBefore do not follow from the vectors (flags %llu)", bad);
     }
     if (N) {
         LoadVerifyArgs v{};
-        v.hb = h->hb;
-        v.la = h->la;
+        v.hb = h->lay.hb;
+        v.la = h->lay.la;
         v.stride = h->stride;
         v.n = (uint32_t)N;
         v.B = B;
-        v.ev_branch = h->ev_branch;
-        v.ev_seq = h->ev_seq;
-        v.branch_first = h->branch_first;
-        v.branch_len = h->branch_len;
-        v.brow = h->brow;
+        v.ev_branch = h->lay.ev_branch;
+        v.ev_seq = h->lay.ev_seq;
+        v.branch_first = h->lay.branch_first;
+        v.branch_len = h->lay.branch_len;
+        v.brow = h->lay.brow;
         v.s_cap = h->s_cap;
         v.bad = h->status + 5;
         HIPCHK(h, hipMemsetAsync(h->status + 5, 0, 4, st));
@@ -3522,17 +3322,17 @@ int lx_index_view(lx_index *h, IndexView *o) {
     }
     o->stream = h->stream;
     o->device = h->device;
-    o->hb = h->hb;
-    o->la = h->la;
+    o->hb = h->lay.hb;
+    o->la = h->lay.la;
     o->stride = h->pstride;
     o->n_events = h->n_events;
     o->V = h->V;
     o->B = h->B;
     o->quorum = h->quorum;
     o->max_seq = h->max_seq;
-    o->wpad = h->wpad;
-    o->ev_branch = h->ev_branch;
-    o->ev_creator = h->ev_creator;
+    o->wpad = h->lay.wpad;
+    o->ev_branch = h->lay.ev_branch;
+    o->ev_creator = h->lay.ev_creator;
     o->weights = &h->weights;
     o->by_creator = &h->by_creator;
     o->shard_count = h->shard_count;

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/lachesis_emitter.h"
+#include "lx_devbuf.h"
 #include "lx_internal.h"
 
 namespace {
@@ -27,17 +28,16 @@ struct lx_qi {
     std::string err;
     uint32_t V = 0, quorum = 0, B = 0;
     bool dirty = true;
-    uint32_t *mt = nullptr, *sp = nullptr, *median = nullptr, *weights = nullptr;
-    int32_t *cheat_of = nullptr;
-    uint32_t *cheat_off = nullptr, *cheat_br = nullptr;
-    uint32_t *d_ev = nullptr, *d_tg = nullptr;
-    unsigned long long *d_out = nullptr;
-    unsigned long long *lastk = nullptr;   // [V + 1] last batch position per creator / self (k_qi_mark)
+    lxi::DevBuf<uint32_t> mt, sp, median, weights;
+    lxi::DevBuf<int32_t> cheat_of;
+    lxi::DevBuf<uint32_t> cheat_off, cheat_br;
+    lxi::DevBuf<uint32_t> d_ev, d_tg;      // a batch's events and targets (d_ev.cap() of them)
+    lxi::DevBuf<unsigned long long> d_out;
+    lxi::DevBuf<unsigned long long> lastk;   // [V + 1] last batch position per creator / self (k_qi_mark)
     uint32_t gen = 0;
     std::vector<uint32_t> stage;           // host image of a large batch: events, then self flags
     hipEvent_t staged = nullptr;           // its copy has read `stage`
     hipEvent_t done = nullptr;             // the last ProcessEvent launch finished (freeing waits for it)
-    uint64_t cap = 0;
 
     int fail(int code, const char *fmt, ...) {
         char buf[512];
@@ -67,21 +67,6 @@ struct lx_qi {
 
 namespace {
 
-void qi_free(lx_qi *q) {
-    void *p[] = {q->mt, q->sp, q->median, q->weights, q->cheat_of, q->cheat_off, q->cheat_br, q->d_ev, q->d_tg,
-                 q->d_out, q->lastk};
-    for (void *x : p)
-        if (x) (void)hipFree(x);
-    q->mt = q->sp = q->median = q->weights = nullptr;
-    q->cheat_of = nullptr;
-    q->cheat_off = q->cheat_br = nullptr;
-    q->d_ev = q->d_tg = nullptr;
-    q->d_out = nullptr;
-    q->lastk = nullptr;
-    q->cap = 0;
-    q->B = 0;
-}
-
 int view(lx_qi *q, IndexView *iv) {
     int rc = lx_index_view(q->ix, iv);
     if (rc) {
@@ -106,11 +91,8 @@ int refresh_cheaters(lx_qi *q, const IndexView &iv) {
         br.insert(br.end(), l.begin(), l.end());
         off.push_back((uint32_t)br.size());
     }
-    if (q->cheat_off) (void)hipFree(q->cheat_off);
-    if (q->cheat_br) (void)hipFree(q->cheat_br);
-    q->cheat_off = q->cheat_br = nullptr;
-    QHIP(q, hipMalloc((void **)&q->cheat_off, off.size() * 4));
-    QHIP(q, hipMalloc((void **)&q->cheat_br, std::max<size_t>(br.size(), 1) * 4));
+    QHIP(q, q->cheat_off.renew(off.size()));
+    QHIP(q, q->cheat_br.renew(br.size()));
     QHIP(q, hipMemcpyAsync(q->cheat_off, off.data(), off.size() * 4, hipMemcpyHostToDevice, iv.stream));
     if (!br.empty()) QHIP(q, hipMemcpyAsync(q->cheat_br, br.data(), br.size() * 4, hipMemcpyHostToDevice, iv.stream));
     QHIP(q, hipMemcpyAsync(q->cheat_of, of.data(), q->V * 4ull, hipMemcpyHostToDevice, iv.stream));
@@ -139,19 +121,13 @@ QiArgs qi_args(lx_qi *q, const IndexView &iv) {
 }
 
 int ensure_cap(lx_qi *q, uint64_t n, hipStream_t s) {
-    if (n <= q->cap) return 0;
+    if (n <= q->d_ev.cap()) return 0;
     const uint64_t cap = std::max<uint64_t>(n, 1024);
     QHIP(q, hipStreamSynchronize(s));   // ProcessEvent launches may still read the old buffers
-    if (q->d_ev) (void)hipFree(q->d_ev);
-    if (q->d_tg) (void)hipFree(q->d_tg);
-    if (q->d_out) (void)hipFree(q->d_out);
-    q->d_ev = q->d_tg = nullptr;
-    q->d_out = nullptr;
-    q->cap = 0;
-    QHIP(q, hipMalloc((void **)&q->d_ev, cap * 4));
-    QHIP(q, hipMalloc((void **)&q->d_tg, cap * 4));
-    QHIP(q, hipMalloc((void **)&q->d_out, cap * 8));
-    q->cap = cap;
+    q->d_ev.reset();   // (the capacity the check above reads: set last)
+    QHIP(q, q->d_tg.renew(cap));
+    QHIP(q, q->d_out.renew(cap));
+    QHIP(q, q->d_ev.renew(cap));
     return 0;
 }
 
@@ -194,7 +170,6 @@ int lx_qi_create(lx_index *index, lx_qi **out) {
 void lx_qi_destroy(lx_qi *q) {
     if (!q) return;
     if (q->done) (void)hipEventSynchronize(q->done);   // ProcessEvent launches in flight
-    qi_free(q);
     if (q->staged) (void)hipEventDestroy(q->staged);
     if (q->done) (void)hipEventDestroy(q->done);
     delete q;
@@ -214,16 +189,17 @@ int lx_qi_reset(lx_qi *q) {
     if (iv.V > kQiMaxV) return q->fail(LX_ERR_ARG, "QuorumIndexer supports up to %u validators", kQiMaxV);
     QHIP(q, hipSetDevice(iv.device));
     if (q->done) QHIP(q, hipEventSynchronize(q->done));   // ProcessEvent launches in flight read the old buffers
-    qi_free(q);
+    for (auto *b : {&q->d_ev, &q->d_tg}) b->reset();   // sized again by the next batch
+    q->d_out.reset();
     q->V = iv.V;
     q->quorum = iv.quorum;
     const uint64_t V = q->V;
-    QHIP(q, hipMalloc((void **)&q->mt, V * V * 4));
-    QHIP(q, hipMalloc((void **)&q->sp, V * 4));
-    QHIP(q, hipMalloc((void **)&q->median, V * 4));
-    QHIP(q, hipMalloc((void **)&q->weights, V * 4));
-    QHIP(q, hipMalloc((void **)&q->cheat_of, V * 4));
-    QHIP(q, hipMalloc((void **)&q->lastk, (V + 1) * 8));
+    QHIP(q, q->mt.renew(V * V));
+    QHIP(q, q->sp.renew(V));
+    QHIP(q, q->median.renew(V));
+    QHIP(q, q->weights.renew(V));
+    QHIP(q, q->cheat_of.renew(V));
+    QHIP(q, q->lastk.renew(V + 1));
     QHIP(q, hipMemsetAsync(q->lastk, 0, (V + 1) * 8, iv.stream));
     q->gen = 0;
     QHIP(q, hipMemsetAsync(q->mt, 0, V * V * 4, iv.stream));

@@ -53,14 +53,15 @@ struct FcCache {
     // the bus; the slots changed since the mirror was written are `dirty`
     // (k_add1_row takes up to kAdd1Delta of them in its arguments, else the
     // mirror is copied before the fill)
-    uint32_t *evk = nullptr;                        // event per slot (free: a valid fallback, 0)
-    uint8_t *g7 = nullptr;                          // column generation per slot, 1..126
-    uint32_t *evk_d = nullptr;                      // device mirrors
-    uint8_t *g7_d = nullptr;
+    PinBuf<uint32_t> evk;   // event per slot (free: a valid fallback, 0)
+    PinBuf<uint8_t> g7;     // column generation per slot, 1..126
+    DU32 evk_d;                                     // device mirrors
+    DBytes g7_d;
     std::vector<uint32_t> dirty;
     std::vector<uint8_t> dmark;
     bool dirty_all = true;
-    uint8_t *M = nullptr, *M_dev = nullptr;         // [W][W], pinned and device-mapped: answers land here
+    MapBuf<uint8_t> M;   // [W][W], pinned and device-mapped: answers land here
+    uint8_t *M_dev = nullptr;                       // M as the device sees it
     // the last fill: it writes row inflight_sa of M (a tile fill: every row)
     // while the host goes on as soon as its own answer landed; a row is reused
     // (cleared for a new occupant) only after that fill has finished.  A fill
@@ -76,7 +77,7 @@ struct FcCache {
     std::vector<uint8_t> g7_launch;                 // the column generations the in-flight row fill writes
     lx_index *h = nullptr;
     // k_add1_row's per-slot {count, sum} words (one per 128-B line), zero between launches
-    uint32_t *d_rsum = nullptr;
+    DU32 d_rsum;
     std::vector<uint32_t> ev;                       // slot -> event (LX_NONE: free)
     std::vector<uint8_t> ref;                       // clock reference bits
     std::vector<uint32_t> free_slots;
@@ -85,9 +86,8 @@ struct FcCache {
     std::vector<uint32_t> slot_of;
     uint32_t last_a = LX_NONE, last_sa = LX_NONE;
     // tile fills: partial sums and the cheaters' branch columns (k_root_fc)
-    uint32_t *d_psum = nullptr;
-    uint64_t psum_cap = 0;
-    uint32_t *d_k = nullptr;                         // kcol | kflag | kw, k_cap entries each
+    DU32 d_psum;
+    DU32 d_k;                                        // kcol | kflag | kw, k_cap entries each
     // k_B: the branch count the columns were built for; 0 = stale.  A drop can
     // remove one creator's fork branch and a later Add give the same branch
     // number to another creator's fork, so every DropNotFlushed clears it
@@ -171,14 +171,7 @@ namespace {
 
 void fcc_free(FcCache *c) {
     if (!c) return;
-    for (void *p : {(void *)c->evk, (void *)c->g7, (void *)c->M})
-        if (p) (void)hipHostFree(p);
-    if (c->evk_d) (void)hipFree(c->evk_d);
-    if (c->g7_d) (void)hipFree(c->g7_d);
     if (c->filled) (void)hipEventDestroy(c->filled);
-    if (c->d_rsum) (void)hipFree(c->d_rsum);
-    if (c->d_psum) (void)hipFree(c->d_psum);
-    if (c->d_k) (void)hipFree(c->d_k);
     delete c;
 }
 
@@ -189,18 +182,14 @@ int fcc_make(lx_index *h) {
     c->W = W;
     c->h = h;
     void *d = nullptr;
-    auto pin = [&](void **host, void **dev, uint64_t bytes) -> hipError_t {
-        hipError_t e = hipHostMalloc(host, bytes, hipHostMallocMapped);
-        if (e != hipSuccess) return e;
-        return hipHostGetDevicePointer(dev, *host, 0);
-    };
-    hipError_t e = hipHostMalloc((void **)&c->evk, 4ull * W, hipHostMallocDefault);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&c->g7, W, hipHostMallocDefault);
-    if (e == hipSuccess) e = hipMalloc((void **)&c->evk_d, 4ull * W);
-    if (e == hipSuccess) e = hipMalloc((void **)&c->g7_d, W);
-    if (e == hipSuccess) { e = pin((void **)&c->M, &d, (uint64_t)W * W); c->M_dev = static_cast<uint8_t *>(d); }
+    hipError_t e = c->evk.renew(W);
+    if (e == hipSuccess) e = c->g7.renew(W);
+    if (e == hipSuccess) e = c->evk_d.renew(W);
+    if (e == hipSuccess) e = c->g7_d.renew(W);
+    if (e == hipSuccess) e = c->M.renew((uint64_t)W * W);
+    if (e == hipSuccess) { e = hipHostGetDevicePointer(&d, c->M, 0); c->M_dev = static_cast<uint8_t *>(d); }
     if (e == hipSuccess) e = hipEventCreateWithFlags(&c->filled, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipMalloc((void **)&c->d_rsum, 8ull * kAdd1PsumStride * W);
+    if (e == hipSuccess) e = c->d_rsum.renew(2ull * kAdd1PsumStride * W);
     if (e == hipSuccess) e = hipMemsetAsync(c->d_rsum, 0, 8ull * kAdd1PsumStride * W, h->stream);
     if (e != hipSuccess) {
         fcc_free(c);
@@ -233,13 +222,8 @@ int fcc_cheaters(lx_index *h, FcCache *c) {
     }
     c->n_k = (uint32_t)col.size();
     if (c->n_k > c->k_cap) {
-        if (c->d_k) {
-            HIPCHK(h, hipStreamSynchronize(h->stream));
-            (void)hipFree(c->d_k);
-        }
-        c->d_k = nullptr;
         c->k_cap = 0;
-        HIPCHK(h, hipMalloc((void **)&c->d_k, 12ull * c->n_k));
+        HIPCHK(h, c->d_k.renew(3ull * c->n_k, h->stream, true));
         c->k_cap = c->n_k;
     }
     if (c->n_k) {
@@ -294,19 +278,10 @@ int fcc_tile(lx_index *h, FcCache *c) {
     const uint32_t col_split = ((ncols + splits - 1) / splits + 31) / 32 * 32;
     const uint32_t n_split = (ncols + col_split - 1) / col_split;
     const uint64_t need = (uint64_t)n_split * n * rp;
-    if (need > c->psum_cap) {
-        if (c->d_psum) {
-            HIPCHK(h, hipStreamSynchronize(h->stream));
-            (void)hipFree(c->d_psum);
-        }
-        c->d_psum = nullptr;
-        c->psum_cap = 0;
-        HIPCHK(h, dalloc(&c->d_psum, need));
-        c->psum_cap = need;
-    }
+    if (need > c->d_psum.cap()) HIPCHK(h, c->d_psum.renew(need, h->stream, true));
     RootFcArgs r{};
-    r.hb = h->hb;
-    r.la = h->la;
+    r.hb = h->lay.hb;
+    r.la = h->lay.la;
     r.stride = h->pstride;
     r.cand = c->evk_d;
     r.n_cand = n;
@@ -314,13 +289,13 @@ int fcc_tile(lx_index *h, FcCache *c) {
     r.n_roots = n;
     r.roots_fallback = c->evk[0];
     r.ncols = ncols;
-    r.wpad = h->wpad;
+    r.wpad = h->lay.wpad;
     r.quorum = h->quorum;
     r.n_k = c->n_k;
     r.kcol = c->d_k;
     r.kflag = c->d_k + c->n_k;
     r.kw = c->d_k + 2ull * c->n_k;
-    r.ev_branch = h->ev_branch;
+    r.ev_branch = h->lay.ev_branch;
     r.psum = c->d_psum;
     r.words = words;
     r.col_split = col_split;

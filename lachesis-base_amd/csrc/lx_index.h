@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/lachesis_hip.h"
+#include "lx_devbuf.h"
 #include "lx_internal.h"
 
 struct FcCache;   // lx_fccache.cpp
@@ -20,12 +21,8 @@ namespace lxi {
 constexpr uint32_t kStatusWords = 64;   // [1] fc bad flag, [2] max seq, [3] pinned-FC sink, [4] unresolved
                                         // branch, [5] load check flags, [8..9] batch error u64, [16..47] jump flags
 
-template <typename T>
-hipError_t dalloc(T **p, uint64_t n) {
-    *p = nullptr;
-    if (!n) n = 1;
-    return hipMalloc((void **)p, n * sizeof(T));
-}
+using DU32 = DevBuf<uint32_t>;
+using DBytes = DevBuf<uint8_t>;   // untyped scratch (its capacity is its size in bytes)
 
 inline uint32_t round_up(uint32_t x, uint32_t m) { return (x + m - 1) / m * m; }
 
@@ -53,21 +50,6 @@ struct NoInitAlloc : std::allocator<T> {
 template <class T>
 using rawvec = std::vector<T, NoInitAlloc<T>>;
 
-// device scratch grown to `need` elements (contents not kept)
-template <typename H, typename T>
-int grow_scratch(H *h, T **p, uint64_t *cap, uint64_t need) {
-    if (*cap >= need && *p) return 0;
-    if (*p) {
-        if (int rc = h->hip(hipStreamSynchronize(h->stream), "grow_scratch sync")) return rc;
-        (void)hipFree(*p);
-        *p = nullptr;
-        *cap = 0;
-    }
-    if (int rc = h->hip(dalloc(p, need), "grow_scratch")) return rc;
-    *cap = need;
-    return 0;
-}
-
 // hipSetDevice costs microseconds per call; every entry point makes sure the
 // handle's device is current, so switch only when it is not
 inline hipError_t set_dev(int device) {
@@ -75,6 +57,71 @@ inline hipError_t set_dev(int device) {
     if (hipGetDevice(&cur) == hipSuccess && cur == device) return hipSuccess;
     return hipSetDevice(device);
 }
+
+// The device buffers whose shape follows the epoch's layout (branch capacity,
+// local columns, event capacity).  lx_reset drops them all at once when the
+// layout changes (free_all: lay = Layout{}); the buffers that live as long as
+// the handle are members of lx_index itself.
+struct Layout {
+    // the planes: hb / la are views.  They are hb_mem / la_mem themselves,
+    // except on a row-segment rank, whose planes hold its own rows only
+    // (rs_planes): there they are virtual bases (own row e at hb + e * pstride,
+    // inside the allocations of rs_mem_rows rows)
+    uint32_t *hb = nullptr, *la = nullptr;
+    DU32 hb_mem, la_mem;
+    uint64_t rs_mem_rows = 0;
+    uint32_t rs_mem_pstride = 0;
+    // per event, per branch
+    DU32 ev_creator, ev_seq, ev_branch, ev_bbefore, ev_sp, first_child;
+    DU32 first_root, branch_first, branch_creator, branch_len, brow, wpad, col_list;
+    // LowestAfter tail zeroing (unsharded; TailArgs): per-(j, c) done-up-to seqs
+    DU32 tail_zw, tail_lo, tail_cmin;
+    uint32_t tail_cap() const { return (uint32_t)tail_cmin.cap(); }
+    DU32 wire_flag;                        // device flag of the byte-wire fit check (4 B)
+    // cheater CSR; cheat_brl / cheat_crl: the same as plane columns (shards)
+    DU32 cheat_off, cheat_br, cheat_creator, cheat_brl, cheat_crl;
+    DevBuf<int32_t> cheat_of;              // creator -> index into the cheater CSR (-1: one branch)
+    // fork-path ForklessCause tables per plane column (k_fc_fk; valid when
+    // fk_hi4 != 0): weight of a non-cheater's original, cheater index of a
+    // cheater's branches, the cheaters' weights
+    DU32 fk_w, fk_c, fk_wch;
+    // column shard (shard_count > 1): own columns only (lx_internal.h)
+    DU32 cmap, lap, wloc;
+    // batch scratch (batch_cap events, b_par.cap() parents)
+    uint64_t batch_cap = 0;
+    DU32 b_creator, b_seq, b_poff, b_par, b_isfork, b_rank, b_tmpbr, b_jmp;
+    DevBuf<EventRec> b_rec;
+    DevBuf<CRec> b_crec;                   // compact records (lx_internal.h) of the last batch
+    DBytes scan_tmp;
+    // query scratch
+    DU32 q_a, q_b;
+    DBytes q_out;
+    // column-shard exchange cache (rows per shard at sc_events)
+    std::vector<DU32> sc_rows;
+    std::vector<uint32_t> sc_nrows;
+    DU32 sc_flag, sc_pos, sc_cols;
+    DBytes sc_tmp;
+    // incremental LowestAfter exchange (lx_shard_dirty*): per branch the events it
+    // had at the last committed exchange; the dirty row lists of every shard
+    DU32 sx_len, sx_dmin, sx_rows, sx_meta;
+    // write-back (lx_writeback_*): dirty-row flags, row lists, byte offsets
+    DU32 wb_flag, wb_pos, wb_la_rows, wb_hb_rows, wb_buf;
+    DevBuf<uint64_t> wb_len, wb_la_off, wb_hb_off;
+    DBytes wb_tmp;
+    // segmented walk (option segments, lx_segment.hip): scratch of the last batch (seg_mf: flags)
+    DU32 seg_jt, seg_cnt, seg_mf, seg_plist, seg_elist;
+    // row-segment rank (lx_rowseg.cpp)
+    DU32 rs_need, rs_req, rs_ctr, rs_ids, rs_out, rs_send;
+    // ForklessCause across ranks (lx_rowseg_fc_*): per event the stamp of its LA
+    // row (2 gen: asked in batch gen, 2 gen + 1: received), route / sort scratch
+    DU32 rs_stamp, rsq_scratch, rsq_list, rsq_ctr;
+    DBytes rsq_tmp;
+    // rows of other ranks a row-segment rank receives go to receive areas
+    // (rows x pstride): HighestBefore rows for the partial fix-up (rs_rhb, row
+    // rs_hslot[x]), LowestAfter rows for one ForklessCause batch (rs_rla, row
+    // rs_lslot[x])
+    DU32 rs_hslot, rs_rhb, rs_lslot, rs_rla;
+};
 
 }  // namespace lxi
 
@@ -92,13 +139,9 @@ struct lx_index {
     uint64_t n_events = 0, n_flushed = 0, hwm = 0;
     uint32_t B = 0, B_flushed = 0;
     uint32_t max_seq = 0;
-    // LowestAfter tail zeroing (unsharded; TailArgs): per-(j, c) done-up-to seqs
     bool la_tail = true;                   // option la_memset=1: zero the whole LA plane at reset instead
-    uint32_t *tail_zw = nullptr, *tail_lo = nullptr, *tail_cmin = nullptr;
-    uint32_t tail_cap = 0;
-    bool tail_dirty = false;               // zw holds progress (a tail pass ran since it was zeroed)
+    bool tail_dirty = false;               // lay.tail_zw holds progress (a tail pass ran since it was zeroed)
     uint32_t wire_force = 0;               // option shard_wire=4: LowestAfter blocks always uint32
-    uint32_t *wire_flag = nullptr;         // device flag of the byte-wire fit check (4 B)
     uint32_t pcols_used = 0;       // plane columns rows may hold non-zero values in (since the last zeroing)
     bool have_epoch = false;
 
@@ -114,76 +157,31 @@ struct lx_index {
     uint64_t cap_hint = 0;
     uint32_t reserve = 0;
 
-    // device state
-    uint32_t *hb = nullptr, *la = nullptr;
-    uint32_t *ev_creator = nullptr, *ev_seq = nullptr, *ev_branch = nullptr, *ev_bbefore = nullptr,
-             *ev_sp = nullptr, *first_child = nullptr;
-    uint32_t *first_root = nullptr, *branch_first = nullptr, *branch_creator = nullptr, *branch_len = nullptr,
-             *brow = nullptr, *wpad = nullptr, *col_list = nullptr;
-    uint32_t *cheat_off = nullptr, *cheat_br = nullptr, *cheat_creator = nullptr;
-    uint32_t *cheat_brl = nullptr, *cheat_crl = nullptr;   // the same as plane columns (shards)
-    int32_t *cheat_of = nullptr;           // creator -> index into the cheater CSR (-1: one branch)
-    uint32_t cheat_of_cap = 0;
+    // device state: the buffers of the current layout, the handle's own below
+    lxi::Layout lay;
     uint32_t n_cheat = 0, ncols = 0;
-    // fork-path ForklessCause tables per plane column (k_fc_fk; valid when
-    // fk_hi4 != 0): weight of a non-cheater's original, cheater index of a
-    // cheater's branches, the cheaters' weights
-    uint32_t *fk_w = nullptr, *fk_c = nullptr, *fk_wch = nullptr;
-    uint64_t fk_cap = 0;
-    uint32_t fk_hi4 = 0;
+    uint32_t fk_hi4 = 0;                   // the fork-path ForklessCause tables (lay.fk_*) are valid
     bool dbl = true;                       // option dbl=0: the column walker for small fork-free batches too
     bool fc_fk = true;                     // option fc_fk=0: the fix-up loop kernel instead
     // column shard (shard_count > 1): own columns only (lx_internal.h)
     std::vector<uint32_t> h_cmap;          // global branch -> plane column / LX_NONE
     uint32_t nloc = 0;                     // plane columns in use
-    uint32_t *cmap = nullptr, *lap = nullptr, *wloc = nullptr;
-    uint32_t cmap_cap = 0;
     bool sharded() const { return shard_count > 1; }
-    uint64_t cheat_cap = 0;
-    uint32_t *status = nullptr;
+    lxi::DU32 status;
 
-    // batch scratch
-    uint64_t batch_cap = 0, par_cap = 0;
-    uint32_t *b_creator = nullptr, *b_seq = nullptr, *b_poff = nullptr, *b_par = nullptr;
-    uint32_t *b_isfork = nullptr, *b_rank = nullptr, *b_tmpbr = nullptr, *b_jmp = nullptr;
-    EventRec *b_rec = nullptr;
-    CRec *b_crec = nullptr;                // compact records (lx_internal.h) of the last batch
-    bool b_crec_ok = false;                // ... written (fork-free, 16-bit branches and seqs)
-    void *scan_tmp = nullptr;
-    size_t scan_bytes = 0;
+    bool b_crec_ok = false;                // lay.b_crec written (fork-free, 16-bit branches and seqs)
 
-    // query scratch
-    uint64_t q_cap = 0;
-    uint32_t *q_a = nullptr, *q_b = nullptr;
-    uint8_t *q_out = nullptr;
-
-    // column-shard exchange cache (rows per shard at sc_events)
+    // column-shard exchange cache (lay.sc_*: rows per shard at sc_events)
     uint64_t sc_events = ~0ull;
     uint32_t sc_B = 0;
-    std::vector<uint32_t *> sc_rows;
-    std::vector<uint32_t> sc_nrows;
-    uint32_t *sc_flag = nullptr, *sc_pos = nullptr, *sc_cols = nullptr;
     std::vector<uint32_t> sc_col_off;    // shard q's columns: sc_cols[sc_col_off[q] .. sc_col_off[q+1])
-    uint64_t sc_cap = 0;
-    void *sc_tmp = nullptr;
-    size_t sc_tmp_bytes = 0;
     uint32_t sc_cols_B = 0;               // branch count sc_cols was built for
-    // incremental LowestAfter exchange (lx_shard_dirty*): per branch the events it
-    // had at the last committed exchange; the dirty row lists of every shard
-    uint32_t *sx_len = nullptr, *sx_dmin = nullptr;
-    uint32_t sx_cap = 0;
+    // incremental LowestAfter exchange (lay.sx_*)
     bool sx_full = true;                  // the next exchange sends whole blocks (reset, drop, load)
     bool sx_active = false;               // pack / unpack / lx_shard_block use the dirty lists
-    uint32_t *sx_rows = nullptr, *sx_meta = nullptr;
-    uint64_t sx_rows_cap = 0, sx_meta_cap = 0;
     std::vector<uint64_t> sx_roff;        // shard q's dirty rows: sx_rows[sx_roff[q] .. sx_roff[q + 1])
 
-    // write-back (lx_writeback_*): dirty-row flags, row lists, byte offsets
-    uint64_t wb_cap = 0, wb_buf_cap = 0;
-    uint32_t *wb_flag = nullptr, *wb_pos = nullptr, *wb_la_rows = nullptr, *wb_hb_rows = nullptr, *wb_buf = nullptr;
-    uint64_t *wb_len = nullptr, *wb_la_off = nullptr, *wb_hb_off = nullptr;
-    void *wb_tmp = nullptr;
-    size_t wb_tmp_bytes = 0;
+    // write-back (lx_writeback_*, lay.wb_*)
     bool wb_ready = false;
     lx_writeback wb{};
     std::string wb_bi;
@@ -214,13 +212,11 @@ struct lx_index {
     // staging images in flight: slot k = a pinned image and its device copy,
     // copied by a kernel on the handle's stream (k_stage)
     static constexpr int kSlots = 4;
-    uint32_t *st_pin[kSlots] = {};
-    uint64_t st_pin_cap[kSlots] = {};
+    lxi::PinBuf<uint32_t> st_pin[kSlots];
     hipEvent_t st_copied[kSlots] = {};     // the copy of slot k finished (its pinned image is free)
     bool st_used[kSlots] = {};
     uint32_t st_next = 0;
-    uint32_t *st_dev[kSlots] = {};
-    uint64_t st_dev_cap[kSlots] = {};
+    lxi::DU32 st_dev[kSlots];
     SmallInlineArgs sm_inl{};              // arguments of the last launch; images of <= kSmallInline words inline
     // restart from the persisted tables (lx_load_rows / lx_load_finish)
     bool loading = false;
@@ -228,12 +224,11 @@ struct lx_index {
     std::vector<uint32_t> ld_par;          // parents of every loaded event (dense)
     std::vector<uint64_t> ld_poff;
     uint32_t ld_B = 0;                     // branches seen so far (max ID + 1)
-    uint8_t *ld_buf = nullptr;             // device staging of a chunk's bytes and offsets
-    uint64_t ld_buf_cap = 0;
+    lxi::DBytes ld_buf;                    // device staging of a chunk's bytes and offsets
 
     // pinned, device-mapped query buffers (per-call ForklessCause, getters)
-    uint8_t *qp = nullptr, *qp_dev = nullptr;
-    uint64_t qp_cap = 0;
+    lxi::MapBuf<uint8_t> qp;
+    uint8_t *qp_dev = nullptr;             // qp as the device sees it
     uint32_t get_tag = 0;                  // completion tag of the last single-row getter
     bool fc_unchecked = false;             // a ForklessCause launch may have flagged status[1] since lx_sync looked
     // the resident single-row server (k_get_server, option get_server)
@@ -243,7 +238,8 @@ struct lx_index {
     // would wait up to its 250-us idle exit); 2 on whatever the handle count
     int srv_opt = 1;
     hipStream_t srv_stream = nullptr;      // its own (high-priority) stream
-    uint64_t *srv_host = nullptr, *srv_dev = nullptr;   // pinned: [0] request word, [1] exited gen
+    lxi::MapBuf<uint64_t> srv_host;   // [0] request word, [1] exited gen
+    uint64_t *srv_dev = nullptr;           // srv_host as the device sees it
     bool srv_live = false;                 // launched and not known to have left
     uint32_t srv_gen = 0;
     GetSrvArgs srv_args{};                 // the live server's arguments (ticks, seen0, gen aside)
@@ -271,17 +267,14 @@ struct lx_index {
     uint32_t segments = 0;
     bool fc_early = true;                  // option fc_early=0: k_fc always reads whole rows
     uint32_t fc_early_lanes = 32;          // option fc_early_lanes: k_fc_early's lanes per query (16 or 32)
-    unsigned long long *d_clk = nullptr;       // walk clock records (IndexArgs::clk)
+    lxi::DevBuf<unsigned long long> d_clk;     // walk clock records (IndexArgs::clk)
     // column-shard early exit (lx_fc_shard_undecided_dev): flags, scan, scan scratch
-    uint32_t *fcs_flag = nullptr, *fcs_pos = nullptr;
-    void *fcs_tmp = nullptr;
-    uint64_t fcs_cap = 0;
-    size_t fcs_tmp_bytes = 0;
-    unsigned long long *d_fc_full = nullptr;   // early exit counters (device): past round 1, past round 2, all
+    lxi::DU32 fcs_flag, fcs_pos;
+    lxi::DBytes fcs_tmp;
+    size_t fcs_tmp_bytes = 0;              // of it, what the scan asks for
+    lxi::DevBuf<unsigned long long> d_fc_full;   // early exit counters (device): past round 1, past round 2, all
     bool seg_auto = true;                  // option seg_auto=0: never split a batch on its own
     uint32_t n_cus = 256;                  // compute units of the device (auto segments)
-    uint32_t *seg_jt = nullptr, *seg_cnt = nullptr, *seg_mf = nullptr, *seg_plist = nullptr, *seg_elist = nullptr;
-    uint64_t seg_jt_cap = 0, seg_cnt_cap = 0, seg_mf_cap = 0, seg_plist_cap = 0, seg_elist_cap = 0;   // seg_mf: flags
     std::vector<hipEvent_t> seg_ev;
     lx_seg_stats seg_stats{};
     // row-segment rank (options seg_rank / seg_count, lx_rowseg.cpp): one batch
@@ -294,33 +287,10 @@ struct lx_index {
     uint32_t rs_sub = 1, rs_sub_opt = 0;
     uint32_t rs_npart[kMaxSegments] = {};   // partial events per own sub-segment
     uint32_t rs_seg_lo[kMaxSegments + 1] = {};
-    uint32_t *rs_need = nullptr, *rs_req = nullptr, *rs_ctr = nullptr, *rs_ids = nullptr, *rs_out = nullptr,
-             *rs_send = nullptr;
-    uint64_t rs_need_cap = 0, rs_req_cap = 0, rs_ids_cap = 0, rs_out_cap = 0, rs_send_cap = 0, rs_ctr_cap = 0;
     uint64_t rs_out_per = 0;               // triples per destination in rs_out
     uint64_t rs_nsend = 0;                 // triples packed in rs_send (lx_rowseg_la)
-    // ForklessCause across ranks (lx_rowseg_fc_*): per event the stamp of its LA
-    // row (2 gen: asked in batch gen, 2 gen + 1: received), the batch counter,
-    // route / sort scratch
-    uint32_t *rs_stamp = nullptr;
-    uint64_t rs_stamp_cap = 0;
-    uint32_t rs_gen = 0;
-    uint32_t *rsq_scratch = nullptr, *rsq_list = nullptr, *rsq_ctr = nullptr;
-    uint64_t rsq_scratch_cap = 0, rsq_list_cap = 0, rsq_ctr_cap = 0;
-    void *rsq_tmp = nullptr;
-    size_t rsq_tmp_bytes = 0;
+    uint32_t rs_gen = 0;                   // ForklessCause batch counter across ranks (lay.rs_stamp)
     uint32_t rsq_nlist = 0;                // distinct remote rows of the last lx_rowseg_fc_need
-    // the planes of a row-segment rank hold its own rows only (rs_planes):
-    // hb / la are virtual bases (own row e at hb + e * pstride, inside the
-    // allocations rs_hb_mem / rs_la_mem of rs_mem_rows rows); rows of other
-    // ranks it receives go to receive areas: HighestBefore rows for the
-    // partial fix-up (rs_rhb, row rs_hslot[x]), LowestAfter rows for one
-    // ForklessCause batch (rs_rla, row rs_lslot[x])
-    uint32_t *rs_hb_mem = nullptr, *rs_la_mem = nullptr;
-    uint64_t rs_mem_rows = 0;
-    uint32_t rs_mem_pstride = 0;
-    uint32_t *rs_hslot = nullptr, *rs_rhb = nullptr, *rs_lslot = nullptr, *rs_rla = nullptr;
-    uint64_t rs_hslot_cap = 0, rs_rhb_cap = 0, rs_lslot_cap = 0, rs_rla_cap = 0;   // (receive areas: rows x pstride)
     bool rowseg() const { return rs_count >= 1; }   // seg_count = 1: one rank, the whole epoch
 
     // the epoch and the options as the walk plan sees them (lx_walk_plan.h)
@@ -365,6 +335,15 @@ struct lx_index {
     } while (0)
 
 
+// device scratch grown to `need` elements (contents not kept; waits for the stream before it frees)
+template <typename T>
+int grow_scratch(lx_index *h, lxi::DevBuf<T> &b, uint64_t need) {
+    if (b.cap() >= need && b) return 0;
+    if (b)
+        if (int rc = h->hip(hipStreamSynchronize(h->stream), "grow_scratch sync")) return rc;
+    return h->hip(b.renew(need), "grow_scratch");
+}
+
 // internal entry points shared by lx_capi.cpp and lx_fccache.cpp
 int lx_fc_args(lx_index *h, uint64_t n, const uint32_t *a, const uint32_t *b, uint8_t *out, uint32_t *partial,
                FcArgs *fa);
@@ -379,8 +358,6 @@ int flush_add1_row(lx_index *h, uint32_t a, uint32_t *evk_dev, uint32_t n_slots,
                    uint32_t *psum_dev, const Add1Delta *delta);   // 1: not applicable
 int rs_begin(lx_index *h, IndexArgs ia, hipStream_t s);   // lx_rowseg.cpp
 int rs_planes(lx_index *h, uint32_t n);          // lx_rowseg.cpp: own rows of an n-event epoch
-void rs_planes_free(lx_index *h);
-void rs_free(lx_index *h);
 void srv_stop(lx_index *h);   // lx_capi.cpp: the resident row server leaves
 void fcc_destroy(lx_index *h);
 void fcc_clear(lx_index *h);                    // Reset: a new epoch

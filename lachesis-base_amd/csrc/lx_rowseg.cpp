@@ -38,8 +38,8 @@ namespace {
 
 SegArgs rs_seg_args(lx_index *h) {
     SegArgs a{};
-    a.hb = h->hb;
-    a.la = h->la;
+    a.hb = h->lay.hb;
+    a.la = h->lay.la;
     a.stride = h->pstride;
     a.B = h->B;
     a.bs = 0;
@@ -47,43 +47,43 @@ SegArgs rs_seg_args(lx_index *h) {
     a.n = h->rs_seg_lo[GS];
     a.G = GS;
     for (uint32_t k = 0; k <= GS; k++) a.seg_lo[k] = h->rs_seg_lo[k];
-    a.ev_branch = h->ev_branch;
-    a.ev_seq = h->ev_seq;
-    a.branch_first = h->branch_first;
-    a.branch_len = h->branch_len;
-    a.brow = h->brow;
+    a.ev_branch = h->lay.ev_branch;
+    a.ev_seq = h->lay.ev_seq;
+    a.branch_first = h->lay.branch_first;
+    a.branch_len = h->lay.branch_len;
+    a.brow = h->lay.brow;
     a.s_cap = h->s_cap;
-    a.jt = h->seg_jt;
-    a.cnt = h->seg_cnt;
-    a.pcount = h->seg_cnt + h->B;
-    a.pflag = h->seg_mf;
-    a.plist = h->seg_plist;
-    a.elist = h->seg_elist;
+    a.jt = h->lay.seg_jt;
+    a.cnt = h->lay.seg_cnt;
+    a.pcount = h->lay.seg_cnt + h->B;
+    a.pflag = h->lay.seg_mf;
+    a.plist = h->lay.seg_plist;
+    a.elist = h->lay.seg_elist;
     a.ecount = a.pcount + GS;
     a.own_seg = h->rs_rank * h->rs_sub;
     a.own_lo = h->rs_lo;
     a.per_rank = h->rs_sub;
-    a.rhb = h->rs_rhb;
-    a.hslot = h->rs_hslot;
+    a.rhb = h->lay.rs_rhb;
+    a.hslot = h->lay.rs_hslot;
     return a;
 }
 
 RsArgs rs_args(lx_index *h) {
     RsArgs r{};
-    r.hb = h->hb;
-    r.la = h->la;
+    r.hb = h->lay.hb;
+    r.la = h->lay.la;
     r.stride = h->pstride;
     r.B = h->B;
     r.lo = h->rs_lo;
     r.hi = h->rs_hi;
-    r.pflag = h->seg_mf + h->rs_lo;
+    r.pflag = h->lay.seg_mf + h->rs_lo;
     r.partials_done = h->rs_state >= 2 ? 1u : 0u;
-    r.need = h->rs_need;
-    r.req = h->rs_req;
-    r.req_count = h->rs_ctr;
-    r.remaining = h->rs_ctr + 1;
-    r.rhb = h->rs_rhb;
-    r.hslot = h->rs_hslot;
+    r.need = h->lay.rs_need;
+    r.req = h->lay.rs_req;
+    r.req_count = h->lay.rs_ctr;
+    r.remaining = h->lay.rs_ctr + 1;
+    r.rhb = h->lay.rs_rhb;
+    r.hslot = h->lay.rs_hslot;
     return r;
 }
 
@@ -111,16 +111,7 @@ RsqArgs rsq_args(const lx_index *h) {
 int rsq_tmp(lx_index *h, uint64_t n) {
     size_t need = 0;
     HIPCHK(h, lx::rsq_tmp_bytes(n ? n : 1, h->rs_count, &need));
-    if (need <= h->rsq_tmp_bytes && h->rsq_tmp) return 0;
-    if (h->rsq_tmp) {
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        (void)hipFree(h->rsq_tmp);
-        h->rsq_tmp = nullptr;
-        h->rsq_tmp_bytes = 0;
-    }
-    HIPCHK(h, hipMalloc(&h->rsq_tmp, need ? need : 1));
-    h->rsq_tmp_bytes = need;
-    return 0;
+    return grow_scratch(h, h->lay.rsq_tmp, need);
 }
 
 int rs_check(lx_index *h, int state) {
@@ -154,51 +145,24 @@ int rs_planes(lx_index *h, uint32_t n) {
     uint32_t lo, hi;
     own_bounds(h, n, &lo, &hi);
     const uint64_t rows = hi - lo;
-    if (!h->rs_hb_mem || rows > h->rs_mem_rows || h->rs_mem_pstride != h->pstride) {
-        rs_planes_free(h);
-        HIPCHK(h, dalloc(&h->rs_hb_mem, rows * h->pstride));
-        HIPCHK(h, dalloc(&h->rs_la_mem, rows * h->pstride));
+    Layout &l = h->lay;
+    if (!l.hb_mem || rows > l.rs_mem_rows || l.rs_mem_pstride != h->pstride) {
+        l.hb = l.la = nullptr;
+        l.rs_mem_rows = l.rs_mem_pstride = 0;
+        HIPCHK(h, l.hb_mem.renew(rows * h->pstride, h->stream, true));   // (the walk may still write the old rows)
+        HIPCHK(h, l.la_mem.renew(rows * h->pstride));
         // a new HB allocation is zeroed here (its pad columns past the
         // epoch's branches are never written by the walk); the LA rows are
         // not: rs_begin zeroes the own rows at every batch before the walk
         // fills them.  Receive-area rows are read only where rs_lslot /
         // rs_hslot stamp them for the current batch.
-        HIPCHK(h, hipMemsetAsync(h->rs_hb_mem, 0, rows * h->pstride * 4, h->stream));
-        h->rs_mem_rows = rows;
-        h->rs_mem_pstride = h->pstride;
+        HIPCHK(h, hipMemsetAsync(l.hb_mem, 0, rows * h->pstride * 4, h->stream));
+        l.rs_mem_rows = rows;
+        l.rs_mem_pstride = h->pstride;
     }
-    h->hb = h->rs_hb_mem - (uint64_t)lo * h->pstride;
-    h->la = h->rs_la_mem - (uint64_t)lo * h->pstride;
+    l.hb = l.hb_mem - (uint64_t)lo * h->pstride;
+    l.la = l.la_mem - (uint64_t)lo * h->pstride;
     return 0;
-}
-
-void rs_planes_free(lx_index *h) {
-    if (!h->rs_hb_mem && !h->rs_la_mem) return;
-    (void)hipStreamSynchronize(h->stream);
-    if (h->rs_hb_mem) (void)hipFree(h->rs_hb_mem);
-    if (h->rs_la_mem) (void)hipFree(h->rs_la_mem);
-    h->rs_hb_mem = h->rs_la_mem = nullptr;
-    h->hb = h->la = nullptr;
-    h->rs_mem_rows = 0;
-    h->rs_mem_pstride = 0;
-}
-
-void rs_free(lx_index *h) {
-    void *p[] = {h->rs_need, h->rs_req, h->rs_ctr, h->rs_ids, h->rs_out, h->rs_send,
-                 h->rs_stamp, h->rsq_scratch, h->rsq_list, h->rsq_ctr, h->rsq_tmp,
-                 h->rs_hslot, h->rs_rhb, h->rs_lslot, h->rs_rla};
-    for (void *q : p)
-        if (q) (void)hipFree(q);
-    h->rs_hslot = h->rs_rhb = h->rs_lslot = h->rs_rla = nullptr;
-    h->rs_hslot_cap = h->rs_rhb_cap = h->rs_lslot_cap = h->rs_rla_cap = 0;
-    h->rs_need = h->rs_req = h->rs_ctr = h->rs_ids = h->rs_out = h->rs_send = nullptr;
-    h->rs_need_cap = h->rs_req_cap = h->rs_ids_cap = h->rs_out_cap = h->rs_send_cap = h->rs_ctr_cap = 0;
-    h->rs_stamp = h->rsq_scratch = h->rsq_list = h->rsq_ctr = nullptr;
-    h->rsq_tmp = nullptr;
-    h->rs_stamp_cap = h->rsq_scratch_cap = h->rsq_list_cap = h->rsq_ctr_cap = 0;
-    h->rsq_tmp_bytes = 0;
-    h->rs_gen = 0;
-    h->rs_state = 0;
 }
 
 // lx_add_batch on a row-segment rank (the epoch's only batch, assigned): walk
@@ -233,15 +197,15 @@ int rs_begin(lx_index *h, IndexArgs ia, hipStream_t s) {
         if (lo != h->rs_lo || hi != h->rs_hi) return h->fail(LX_ERR_STATE, "row-segment bounds disagree with the planes");
     }
     int rc;
-    if ((rc = grow_scratch(h, &h->seg_jt, &h->seg_jt_cap, (uint64_t)(G * S + 1) * h->B)) ||
-        (rc = grow_scratch(h, &h->seg_cnt, &h->seg_cnt_cap, (uint64_t)h->B + 2 * kMaxSegments)) ||
-        (rc = grow_scratch(h, &h->seg_mf, &h->seg_mf_cap, (uint64_t)n)) ||
-        (rc = grow_scratch(h, &h->seg_plist, &h->seg_plist_cap, (uint64_t)n)) ||
-        (rc = grow_scratch(h, &h->seg_elist, &h->seg_elist_cap, (uint64_t)n)) ||
-        (rc = grow_scratch(h, &h->rs_need, &h->rs_need_cap, (uint64_t)n)) ||
-        (rc = grow_scratch(h, &h->rs_hslot, &h->rs_hslot_cap, (uint64_t)n)) ||
-        (rc = grow_scratch(h, &h->rs_lslot, &h->rs_lslot_cap, (uint64_t)n)) ||
-        (rc = grow_scratch(h, &h->rs_ctr, &h->rs_ctr_cap, (uint64_t)2 + 2 * kMaxSegments)))
+    if ((rc = grow_scratch(h, h->lay.seg_jt, (uint64_t)(G * S + 1) * h->B)) ||
+        (rc = grow_scratch(h, h->lay.seg_cnt, (uint64_t)h->B + 2 * kMaxSegments)) ||
+        (rc = grow_scratch(h, h->lay.seg_mf, (uint64_t)n)) ||
+        (rc = grow_scratch(h, h->lay.seg_plist, (uint64_t)n)) ||
+        (rc = grow_scratch(h, h->lay.seg_elist, (uint64_t)n)) ||
+        (rc = grow_scratch(h, h->lay.rs_need, (uint64_t)n)) ||
+        (rc = grow_scratch(h, h->lay.rs_hslot, (uint64_t)n)) ||
+        (rc = grow_scratch(h, h->lay.rs_lslot, (uint64_t)n)) ||
+        (rc = grow_scratch(h, h->lay.rs_ctr, (uint64_t)2 + 2 * kMaxSegments)))
         return rc;
     while (h->seg_ev.size() < 6) {
         hipEvent_t e;
@@ -250,17 +214,17 @@ int rs_begin(lx_index *h, IndexArgs ia, hipStream_t s) {
     }
     h->rs_state = 0;
     // no LowestAfter row of another segment has been received in this epoch
-    if ((rc = grow_scratch(h, &h->rs_stamp, &h->rs_stamp_cap, (uint64_t)n))) return rc;
-    HIPCHK(h, hipMemsetAsync(h->rs_stamp, 0, (uint64_t)n * 4, s));
+    if ((rc = grow_scratch(h, h->lay.rs_stamp, (uint64_t)n))) return rc;
+    HIPCHK(h, hipMemsetAsync(h->lay.rs_stamp, 0, (uint64_t)n * 4, s));
     h->rs_gen = 0;
     SegArgs a = rs_seg_args(h);
     HIPCHK(h, lx::launch_seg_tables(a, s));
     // the own rows' LowestAfter is written by the own pass and the others' triples only
-    HIPCHK(h, hipMemsetAsync(h->la + (uint64_t)h->rs_lo * h->pstride, 0,
+    HIPCHK(h, hipMemsetAsync(h->lay.la + (uint64_t)h->rs_lo * h->pstride, 0,
                              (uint64_t)(h->rs_hi - h->rs_lo) * h->pstride * 4, s));
     ia.seg = 1;
-    ia.ev_branch = h->ev_branch;
-    ia.ev_seq = h->ev_seq;
+    ia.ev_branch = h->lay.ev_branch;
+    ia.ev_seq = h->lay.ev_seq;
     ia.seg_j = a.jt;
     ia.seg_flag = a.pflag;
     ia.seg_list = a.plist;
@@ -288,20 +252,20 @@ int rs_begin(lx_index *h, IndexArgs ia, hipStream_t s) {
     // the rows to ask for: at most every referenced branch of every partial
     // event plus one per branch, and never more than the events before lo
     const uint64_t want = std::min<uint64_t>((uint64_t)h->rs_npartial * h->B + h->B, (uint64_t)h->rs_lo + 1);
-    if ((rc = grow_scratch(h, &h->rs_req, &h->rs_req_cap, want)) ||
-        (rc = grow_scratch(h, &h->rs_ids, &h->rs_ids_cap, want)))
+    if ((rc = grow_scratch(h, h->lay.rs_req, want)) ||
+        (rc = grow_scratch(h, h->lay.rs_ids, want)))
         return rc;
-    HIPCHK(h, hipMemsetAsync(h->rs_need, 0, (uint64_t)n * 4, s));
-    HIPCHK(h, hipMemsetAsync(h->rs_ctr, 0, (2 + 2 * kMaxSegments) * 4, s));
+    HIPCHK(h, hipMemsetAsync(h->lay.rs_need, 0, (uint64_t)n * 4, s));
+    HIPCHK(h, hipMemsetAsync(h->lay.rs_ctr, 0, (2 + 2 * kMaxSegments) * 4, s));
     RsArgs r = rs_args(h);
     HIPCHK(h, lx::launch_rs_refs(a, r, h->rs_npart, s));
-    HIPCHK(h, hipMemcpyAsync(h->rs_ctr + 1, h->rs_ctr, 4, hipMemcpyDeviceToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(h->lay.rs_ctr + 1, h->lay.rs_ctr, 4, hipMemcpyDeviceToDevice, s));
     uint32_t nreq = 0;
-    HIPCHK(h, hipMemcpyAsync(&nreq, h->rs_ctr, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(&nreq, h->lay.rs_ctr, 4, hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipStreamSynchronize(s));
     h->rs_nreq = nreq;
     // the receive area: one row per distinct requested row (rs_hslot set by k_rs_refs)
-    if ((rc = grow_scratch(h, &h->rs_rhb, &h->rs_rhb_cap, (uint64_t)std::max<uint32_t>(nreq, 1) * h->pstride)))
+    if ((rc = grow_scratch(h, h->lay.rs_rhb, (uint64_t)std::max<uint32_t>(nreq, 1) * h->pstride)))
         return rc;
     lx_seg_stats &st = h->seg_stats;
     st = lx_seg_stats{};
@@ -340,8 +304,8 @@ int lx_rowseg_requests(lx_index *h, uint32_t *ids, uint32_t cap, uint32_t *count
     if (ids && cap < h->rs_nreq) return h->fail(LX_ERR_ARG, "request buffer of %u ids < %u", cap, h->rs_nreq);
     SegArgs a = rs_seg_args(h);
     RsArgs r = rs_args(h);
-    HIPCHK(h, lx::launch_rs_bucket(a, r, h->rs_nreq, ids ? ids : h->rs_ids, h->rs_ctr + 2, h->stream));
-    HIPCHK(h, hipMemcpyAsync(counts, h->rs_ctr + 2, h->rs_count * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, lx::launch_rs_bucket(a, r, h->rs_nreq, ids ? ids : h->lay.rs_ids, h->lay.rs_ctr + 2, h->stream));
+    HIPCHK(h, hipMemcpyAsync(counts, h->lay.rs_ctr + 2, h->rs_count * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return 0;
 }
@@ -371,7 +335,7 @@ int lx_rowseg_receive(lx_index *h, uint32_t n, const uint32_t *ids, const uint32
     if (h->rs_state == 1) {
         RsArgs r = rs_args(h);
         HIPCHK(h, lx::launch_rs_scatter(r, ids, n, rows, ready, h->stream));
-        HIPCHK(h, hipMemcpyAsync(&left, h->rs_ctr + 1, 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(&left, h->lay.rs_ctr + 1, 4, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
         if (!left && (rc = rs_fix_partials(h))) return rc;
     }
@@ -397,9 +361,9 @@ int lx_rowseg_la(lx_index *h, uint64_t *counts) {
     HIPCHK(h, hipMemcpyAsync(ne, a.ecount + k0, 4ull * S, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     for (int attempt = 0; attempt < 2; attempt++) {
-        if ((rc = grow_scratch(h, &h->rs_out, &h->rs_out_cap, 3ull * G * h->rs_out_per))) return rc;
-        a.out = h->rs_out;
-        a.out_count = h->rs_ctr + 2 + kMaxSegments;
+        if ((rc = grow_scratch(h, h->lay.rs_out, 3ull * G * h->rs_out_per))) return rc;
+        a.out = h->lay.rs_out;
+        a.out_count = h->lay.rs_ctr + 2 + kMaxSegments;
         a.out_cap = h->rs_out_per;
         HIPCHK(h, hipMemsetAsync(a.out_count, 0, G * 4, h->stream));
         for (uint32_t t = 0; t < S; t++) HIPCHK(h, lx::launch_seg_la_edge(a, k0 + t, ne[t], h->stream));
@@ -416,12 +380,12 @@ int lx_rowseg_la(lx_index *h, uint64_t *counts) {
     HIPCHK(h, hipEventElapsedTime(&h->seg_stats.la_ms, h->seg_ev[4], h->seg_ev[5]));
     uint64_t tot = 0;
     for (uint32_t q = 0; q < G; q++) tot += c[q];
-    if ((rc = grow_scratch(h, &h->rs_send, &h->rs_send_cap, 3 * tot + 3))) return rc;
+    if ((rc = grow_scratch(h, h->lay.rs_send, 3 * tot + 3))) return rc;
     uint64_t o = 0;
     for (uint32_t q = 0; q < G; q++) {
         counts[q] = c[q];
         if (c[q])
-            HIPCHK(h, hipMemcpyAsync(h->rs_send + 3 * o, h->rs_out + 3ull * q * h->rs_out_per, 12ull * c[q],
+            HIPCHK(h, hipMemcpyAsync(h->lay.rs_send + 3 * o, h->lay.rs_out + 3ull * q * h->rs_out_per, 12ull * c[q],
                                      hipMemcpyDeviceToDevice, h->stream));
         o += c[q];
     }
@@ -435,7 +399,7 @@ int lx_rowseg_la_fetch(lx_index *h, uint32_t *triples) {
     int rc;
     if ((rc = rs_check(h, 3))) return rc;
     if (h->rs_nsend)
-        HIPCHK(h, hipMemcpyAsync(triples, h->rs_send, 12ull * h->rs_nsend, hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(triples, h->lay.rs_send, 12ull * h->rs_nsend, hipMemcpyDeviceToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return 0;
 }
@@ -454,18 +418,18 @@ int lx_rowseg_finish(lx_index *h) {
     if ((rc = rs_check(h, 3))) return rc;
     if (h->B > h->V && h->n_cheat) {
         MarkArgs m{};
-        m.hb = h->hb;
+        m.hb = h->lay.hb;
         m.stride = h->pstride;
         m.cmap = nullptr;
         m.batch_start = h->rs_lo;
         m.n = h->rs_hi - h->rs_lo;
         m.V = h->V;
-        m.ev_branch = h->ev_branch;
-        m.ev_bbefore = h->ev_bbefore;
-        m.branch_first = h->branch_first;
+        m.ev_branch = h->lay.ev_branch;
+        m.ev_bbefore = h->lay.ev_bbefore;
+        m.branch_first = h->lay.branch_first;
         m.n_cheat = h->n_cheat;
-        m.cheat_off = h->cheat_off;
-        m.cheat_br = h->cheat_br;
+        m.cheat_off = h->lay.cheat_off;
+        m.cheat_br = h->lay.cheat_br;
         HIPCHK(h, lx::launch_marks(m, h->stream));
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -482,14 +446,14 @@ int lx_rowseg_fc_route(lx_index *h, uint64_t n, const uint32_t *qa, const uint32
     if (!counts || (n && (!qa || !qb || !ra || !rb || !perm))) return LX_ERR_ARG;
     if (n >= 0x7FFFFFFFull) return h->fail(LX_ERR_ARG, "too many queries in one batch");
     const uint32_t G = h->rs_count;
-    if ((rc = grow_scratch(h, &h->rsq_scratch, &h->rsq_scratch_cap, 3 * n + 3)) ||
-        (rc = grow_scratch(h, &h->rsq_ctr, &h->rsq_ctr_cap, (uint64_t)2 * kMaxSegments + 2)) || (rc = rsq_tmp(h, n)))
+    if ((rc = grow_scratch(h, h->lay.rsq_scratch, 3 * n + 3)) ||
+        (rc = grow_scratch(h, h->lay.rsq_ctr, (uint64_t)2 * kMaxSegments + 2)) || (rc = rsq_tmp(h, n)))
         return rc;
     const RsqArgs a = rsq_args(h);
-    HIPCHK(h, lx::launch_rsq_route(a, qa, qb, n, h->rsq_scratch, h->rsq_tmp, h->rsq_tmp_bytes, ra, rb, perm, h->rsq_ctr,
-                                   h->stream));
+    HIPCHK(h, lx::launch_rsq_route(a, qa, qb, n, h->lay.rsq_scratch, h->lay.rsq_tmp, h->lay.rsq_tmp.cap(), ra, rb, perm,
+                                   h->lay.rsq_ctr, h->stream));
     uint32_t c[kMaxSegments];
-    HIPCHK(h, hipMemcpyAsync(c, h->rsq_ctr, 4ull * G, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(c, h->lay.rsq_ctr, 4ull * G, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     for (uint32_t q = 0; q < G; q++) counts[q] = c[q];
     return 0;
@@ -502,27 +466,28 @@ int lx_rowseg_fc_need(lx_index *h, uint64_t m, const uint32_t *ra, const uint32_
     if (!counts || (m && (!ra || !rb))) return LX_ERR_ARG;
     const uint32_t G = h->rs_count;
     if (h->rs_gen >= 0x7FFFFFF0u) {   // stamps about to wrap: forget every received row
-        HIPCHK(h, hipMemsetAsync(h->rs_stamp, 0, h->n_events * 4, h->stream));
+        HIPCHK(h, hipMemsetAsync(h->lay.rs_stamp, 0, h->n_events * 4, h->stream));
         h->rs_gen = 0;
     }
     h->rs_gen++;
     const uint64_t lim = std::min<uint64_t>(m, h->n_events);
-    if ((rc = grow_scratch(h, &h->rsq_list, &h->rsq_list_cap, lim + 1)) ||
-        (rc = grow_scratch(h, &h->rsq_ctr, &h->rsq_ctr_cap, (uint64_t)2 * kMaxSegments + 2)))
+    if ((rc = grow_scratch(h, h->lay.rsq_list, lim + 1)) ||
+        (rc = grow_scratch(h, h->lay.rsq_ctr, (uint64_t)2 * kMaxSegments + 2)))
         return rc;
     const RsqArgs a = rsq_args(h);
-    uint32_t *cnt = h->rsq_ctr + kMaxSegments;
+    uint32_t *cnt = h->lay.rsq_ctr + kMaxSegments;
     HIPCHK(h, hipMemsetAsync(cnt, 0, 4, h->stream));
-    HIPCHK(h, lx::launch_rsq_need(a, ra, rb, m, h->rs_stamp, 2 * h->rs_gen, h->rsq_list, cnt, h->stream));
+    HIPCHK(h, lx::launch_rsq_need(a, ra, rb, m, h->lay.rs_stamp, 2 * h->rs_gen, h->lay.rsq_list, cnt, h->stream));
     uint32_t nl = 0;
     HIPCHK(h, hipMemcpyAsync(&nl, cnt, 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->rsq_nlist = nl;
     if (nl && (!ids || cap < nl)) return h->fail(LX_ERR_ARG, "id buffer of %llu < %u rows", (unsigned long long)cap, nl);
     if ((rc = rsq_tmp(h, nl))) return rc;
-    HIPCHK(h, lx::launch_rsq_group(a, h->rsq_list, nl, h->rsq_tmp, h->rsq_tmp_bytes, ids, h->rsq_ctr, h->stream));
+    HIPCHK(h, lx::launch_rsq_group(a, h->lay.rsq_list, nl, h->lay.rsq_tmp, h->lay.rsq_tmp.cap(), ids, h->lay.rsq_ctr,
+                                   h->stream));
     uint32_t c[kMaxSegments];
-    HIPCHK(h, hipMemcpyAsync(c, h->rsq_ctr, 4ull * G, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(c, h->lay.rsq_ctr, 4ull * G, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     for (uint32_t q = 0; q < G; q++) counts[q] = c[q];
     return 0;
@@ -533,7 +498,7 @@ int lx_rowseg_la_serve(lx_index *h, uint64_t n, const uint32_t *ids, uint32_t *r
     if ((rc = rs_check(h, 4))) return rc;
     if (n && (!ids || !rows)) return LX_ERR_ARG;
     if (n > 0xFFFFFFFFull) return LX_ERR_ARG;
-    HIPCHK(h, lx::launch_rsq_la_gather(rsq_args(h), h->la, h->pstride, ids, (uint32_t)n, rows, h->stream));
+    HIPCHK(h, lx::launch_rsq_la_gather(rsq_args(h), h->lay.la, h->pstride, ids, (uint32_t)n, rows, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return 0;
 }
@@ -544,9 +509,9 @@ int lx_rowseg_la_store(lx_index *h, uint64_t n, const uint32_t *ids, const uint3
     if (n && (!ids || !rows)) return LX_ERR_ARG;
     if (n > 0xFFFFFFFFull) return LX_ERR_ARG;
     // the batch's receive area: row i = ids[i] (one store per batch, after lx_rowseg_fc_need)
-    if ((rc = grow_scratch(h, &h->rs_rla, &h->rs_rla_cap, std::max<uint64_t>(n, 1) * h->pstride))) return rc;
-    HIPCHK(h, lx::launch_rsq_la_store(rsq_args(h), h->rs_rla, h->pstride, ids, (uint32_t)n, rows, h->rs_stamp,
-                                      h->rs_lslot, 2 * h->rs_gen + 1, h->stream));
+    if ((rc = grow_scratch(h, h->lay.rs_rla, std::max<uint64_t>(n, 1) * h->pstride))) return rc;
+    HIPCHK(h, lx::launch_rsq_la_store(rsq_args(h), h->lay.rs_rla, h->pstride, ids, (uint32_t)n, rows, h->lay.rs_stamp,
+                                      h->lay.rs_lslot, 2 * h->rs_gen + 1, h->stream));
     return 0;
 }
 

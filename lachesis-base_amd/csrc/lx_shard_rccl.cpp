@@ -98,21 +98,16 @@ struct lx_shard_comm {
     hipStream_t stream = nullptr;
     int device = 0;
     uint32_t rank = 0, nranks = 1;
-    uint8_t *send = nullptr, *recv = nullptr;    // exchange staging (bytes), grown on demand
-    size_t send_cap = 0, recv_cap = 0;
-    uint8_t *mbuf = nullptr;                     // element-wise min of the dirty rows (incremental exchange)
-    size_t mbuf_cap = 0;
-    uint32_t *part = nullptr;                    // FC partial sums, grown on demand
-    uint64_t part_cap = 0;
-    uint8_t *ebuf = nullptr;                     // FC early exit: mask, idx, a, b, partials (grown on demand)
-    size_t ecap = 0;
+    lxi::DBytes send, recv;                      // exchange staging (bytes), grown on demand
+    lxi::DBytes mbuf;                            // element-wise min of the dirty rows (incremental exchange)
+    lxi::DU32 part;                              // FC partial sums, grown on demand
+    lxi::DBytes ebuf;                            // FC early exit: mask, idx, a, b, partials (grown on demand)
     uint64_t last_undecided = 0;                 // FC early exit: queries the last call sent to every shard
-    uint32_t *wdev = nullptr;                    // wire widths: [0, G) sent, [G, 2G) received
+    lxi::DU32 wdev;                              // wire widths: [0, G) sent, [G, 2G) received
     lx::ExchangeState xs;                        // byte-wire fallbacks remembered per destination
     bool rowseg = false;                         // a row-segment rank (lx_rowseg_comm_create)
-    uint8_t *rbuf[lx::kRsBufs] = {};             // row-segment exchange buffers, grown on demand
-    size_t rcap[lx::kRsBufs] = {};
-    uint64_t *udev = nullptr;                    // row segments: [0, G) counts sent, [G, 2G) received, [2G] sum
+    lxi::DBytes rbuf[lx::kRsBufs];               // row-segment exchange buffers, grown on demand
+    lxi::DevBuf<uint64_t> udev;                  // row segments: [0, G) counts sent, [G, 2G) received, [2G] sum
     std::string err;
 
     int fail(int code, const char *fmt, ...) {
@@ -136,17 +131,10 @@ struct lx_shard_comm {
         if (rc == 0) return 0;
         return fail(rc, "%s: %s", what, lx_last_error(ix));
     }
-    int grow(uint8_t **p, size_t *cap, size_t need) {
-        if (need <= *cap) return 0;
-        if (*p) {
-            (void)hipStreamSynchronize(stream);
-            (void)hipFree(*p);
-            *p = nullptr;
-            *cap = 0;
-        }
-        if (int rc = hip(hipMalloc(reinterpret_cast<void **>(p), need), "hipMalloc")) return rc;
-        *cap = need;
-        return 0;
+    // contents dropped; the stream may still use the old block
+    template <typename T>
+    int grow(lxi::DevBuf<T> &b, uint64_t need) {
+        return need <= b.cap() ? 0 : hip(b.renew(need, stream, true), "hipMalloc");
     }
 };
 
@@ -224,14 +212,6 @@ void lx_shard_comm_destroy(lx_shard_comm *c) {
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->comm) rccl().CommDestroy(c->comm);
-    (void)hipFree(c->send);
-    (void)hipFree(c->recv);
-    (void)hipFree(c->mbuf);
-    (void)hipFree(c->part);
-    (void)hipFree(c->ebuf);
-    (void)hipFree(c->wdev);
-    for (uint8_t *p : c->rbuf) (void)hipFree(p);
-    (void)hipFree(c->udev);
     delete c;
 }
 
@@ -267,8 +247,8 @@ struct RcclOps {
         return c->index(lx_shard_dirty_set(c->ix, nb, dmin), "lx_shard_dirty_set");
     }
     int commit() { return c->index(lx_shard_dirty_commit(c->ix), "lx_shard_dirty_commit"); }
-    uint8_t *send_buf(size_t n) { return c->grow(&c->send, &c->send_cap, std::max<size_t>(n, 1)) ? nullptr : c->send; }
-    uint8_t *recv_buf(size_t n) { return c->grow(&c->recv, &c->recv_cap, std::max<size_t>(n, 1)) ? nullptr : c->recv; }
+    uint8_t *send_buf(size_t n) { return c->grow(c->send, std::max<size_t>(n, 1)) ? nullptr : c->send.get(); }
+    uint8_t *recv_buf(size_t n) { return c->grow(c->recv, std::max<size_t>(n, 1)) ? nullptr : c->recv.get(); }
 };
 
 // the collectives: grouped ncclSend / ncclRecv on the index stream; ncclGroupEnd
@@ -300,7 +280,7 @@ struct RcclNet {
         return c->hip(hipStreamSynchronize(c->stream), "hipStreamSynchronize");
     }
     int min_u32(uint32_t *v, uint32_t n) {
-        LXC(c->grow(&c->mbuf, &c->mbuf_cap, 4ull * n));
+        LXC(c->grow(c->mbuf, 4ull * n));
         LXC(c->hip(hipMemcpyAsync(c->mbuf, v, 4ull * n, hipMemcpyHostToDevice, c->stream), "hipMemcpyAsync"));
         LXC(c->nccl(rccl().AllReduce(c->mbuf, c->mbuf, n, ncclUint32, ncclMin, c->comm, c->stream), "ncclAllReduce"));
         LXC(c->hip(hipMemcpyAsync(v, c->mbuf, 4ull * n, hipMemcpyDeviceToHost, c->stream), "hipMemcpyAsync"));
@@ -328,7 +308,7 @@ int lx_shard_exchange(lx_shard_comm *c) {
     LXC(c->hip(hipSetDevice(c->device), "hipSetDevice"));
     const uint32_t G = c->nranks;
     if (G == 1) return 0;   // an unsharded handle holds whole LowestAfter rows already
-    if (!c->wdev) LXC(c->hip(hipMalloc(reinterpret_cast<void **>(&c->wdev), 8ull * G), "hipMalloc"));
+    LXC(c->hip(c->wdev.grow(2ull * G), "hipMalloc"));
     RcclOps ops{c};
     RcclNet net{c};
     c->err.clear();
@@ -361,19 +341,13 @@ int lx_forkless_cause_sharded_dev(lx_shard_comm *c, uint64_t n, const uint32_t *
     LXC(c->hip(hipSetDevice(c->device), "hipSetDevice"));
     if (c->nranks == 1)
         return c->index(lx_forkless_cause_batch_dev(c->ix, n, a, b, out, nullptr), "lx_forkless_cause_batch_dev");
-    if (n > c->part_cap) {
-        uint8_t *p = reinterpret_cast<uint8_t *>(c->part);
-        size_t cap = c->part_cap * 4;
-        LXC(c->grow(&p, &cap, n * 4));
-        c->part = reinterpret_cast<uint32_t *>(p);
-        c->part_cap = n;
-    }
+    LXC(c->grow(c->part, n));
     if (n >= kShardEarlyMin && lx_fc_shard_early(c->ix, nullptr)) {
         // early exit: shard 0 decides most queries alone, the
         // others add partials for the rest only
         const uint64_t W = (n + 63) / 64;
-        LXC(c->grow(&c->ebuf, &c->ecap, 16 * W + 16 * n));
-        uint64_t *mask = reinterpret_cast<uint64_t *>(c->ebuf);
+        LXC(c->grow(c->ebuf, 16 * W + 16 * n));
+        uint64_t *mask = reinterpret_cast<uint64_t *>(c->ebuf.get());
         uint32_t *idx = reinterpret_cast<uint32_t *>(c->ebuf + 16 * W);
         uint32_t *a2 = idx + n, *b2 = a2 + n, *p2 = b2 + n;
         const bool s0 = c->rank == 0;
@@ -440,7 +414,7 @@ struct RcclRowOps {
     int la_fetch(uint32_t *buf) { return c->index(lx_rowseg_la_fetch(c->ix, buf), "lx_rowseg_la_fetch"); }
     int la_apply(uint64_t n, const uint32_t *buf) { return c->index(lx_rowseg_la_apply(c->ix, n, buf), "lx_rowseg_la_apply"); }
     int finish() { return c->index(lx_rowseg_finish(c->ix), "lx_rowseg_finish"); }
-    void *buf(int k, size_t bytes) { return c->grow(&c->rbuf[k], &c->rcap[k], bytes) ? nullptr : c->rbuf[k]; }
+    void *buf(int k, size_t bytes) { return c->grow(c->rbuf[k], bytes) ? nullptr : c->rbuf[k].get(); }
     // ForklessCause across ranks (rowseg_fc_run)
     uint32_t rank() const { return c->rank; }
     int fc_route(uint64_t n, const uint32_t *qa, const uint32_t *qb, uint32_t *ra, uint32_t *rb, uint32_t *perm,
@@ -544,7 +518,7 @@ int lx_rowseg_exchange(lx_shard_comm *c, uint64_t stats[4]) {
     bool whole = false;
     LXC(rs_whole(c, &whole));
     if (whole) return 0;   // a whole index: nothing to join
-    if (!c->udev) LXC(c->hip(hipMalloc(reinterpret_cast<void **>(&c->udev), 8ull * (2 * G + 1)), "hipMalloc"));
+    LXC(c->hip(c->udev.grow(2 * G + 1), "hipMalloc"));
     RcclRowOps ops{c};
     RcclRowNet net{c};
     c->err.clear();
@@ -575,7 +549,7 @@ int lx_rowseg_forkless_cause(lx_shard_comm *c, uint64_t n, const uint32_t *qa, c
         LXC(c->index(lx_forkless_cause_batch_dev(c->ix, n, qa, qb, out, nullptr), "lx_forkless_cause_batch_dev"));
         return c->index(lx_sync(c->ix), "lx_sync");
     }
-    if (!c->udev) LXC(c->hip(hipMalloc(reinterpret_cast<void **>(&c->udev), 8ull * (2 * G + 1)), "hipMalloc"));
+    LXC(c->hip(c->udev.grow(2 * G + 1), "hipMalloc"));
     RcclRowOps ops{c};
     RcclRowNet net{c};
     c->err.clear();
@@ -612,7 +586,7 @@ int lx_rowseg_get_rows(lx_shard_comm *c, uint32_t mode, uint64_t n, const uint32
         if (n > 0xFFFFFFFFull) return c->fail(LX_ERR_ARG, "too many rows in one call");
         return c->index(lx_get_rows_dev(c->ix, mode, (uint32_t)n, ev, out, slot, len), "lx_get_rows_dev");
     }
-    if (!c->udev) LXC(c->hip(hipMalloc(reinterpret_cast<void **>(&c->udev), 8ull * (2 * G + 1)), "hipMalloc"));
+    LXC(c->hip(c->udev.grow(2 * G + 1), "hipMalloc"));
     RcclRowOps ops{c};
     RcclRowNet net{c};
     c->err.clear();
