@@ -238,7 +238,7 @@ struct lx_abft {
     DVec<RootFcArgs> d_fcargs;            // merged frame steps of a claimed batch: per-step args
     DVec<QuorumArgs> d_qargs;
     uint32_t n_k = 0;
-    uint32_t k_B = NONE;                // branch count the cheater columns were built for
+    uint64_t k_gen = 0;                 // branch_gen the cheater columns were built for; 0 = stale
     std::vector<uint32_t> h_row;
     bool dec_dirty = true;
     uint32_t vw = 0;                    // subject window [0, vw) of the current election
@@ -439,7 +439,7 @@ void clear_epoch(lx_abft *a) {
     a->last_decided = 0;
     a->t_prev = 0;
     a->dec_dirty = true;
-    a->k_B = NONE;
+    a->k_gen = 0;
 }
 
 int start_epoch(lx_abft *a, uint32_t epoch, uint32_t nv, const uint32_t *w) {
@@ -459,7 +459,7 @@ int start_epoch(lx_abft *a, uint32_t epoch, uint32_t nv, const uint32_t *w) {
 
 // Cheaters' branch columns, grouped by creator, original first (k_root_fc).
 int refresh_cheaters(lx_abft *a, const IndexView &iv) {
-    if (a->k_B == iv.B) return 0;
+    if (a->k_gen == iv.branch_gen) return 0;
     std::vector<uint32_t> col, flag, kw;
     for (uint32_t c = 0; c < iv.V; c++) {
         const auto &l = (*iv.by_creator)[c];
@@ -476,7 +476,7 @@ int refresh_cheaters(lx_abft *a, const IndexView &iv) {
         ARC(upload(a, a->d_kflag, flag, 0, iv.stream));
         ARC(upload(a, a->d_kw, kw, 0, iv.stream));
     }
-    a->k_B = iv.B;
+    a->k_gen = iv.branch_gen;
     return 0;
 }
 

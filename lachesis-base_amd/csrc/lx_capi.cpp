@@ -57,7 +57,7 @@ void free_all(lx_index *h) {
     h->wb_ready = false;
     h->fk_hi4 = 0;
     h->sc_events = ~0ull;
-    h->sc_cols_B = 0;
+    h->sc_cols_gen = 0;
     h->sx_full = true;
     h->sx_active = false;
     h->rs_gen = 0;
@@ -233,8 +233,11 @@ int ensure_batch(lx_index *h, uint64_t n, uint64_t npar) {
     return 0;
 }
 
-// column list of this shard + cheater CSR (restricted to owned creators)
+// column list of this shard + cheater CSR (restricted to owned creators); runs
+// whenever the branch -> creator map changed, so it starts the map's next
+// generation (lx_index.h)
 int rebuild_columns(lx_index *h) {
+    h->branch_gen++;
     std::vector<uint32_t> cols;
     for (uint32_t b = 0; b < h->B; b++) {
         uint32_t c = h->h_branch_creator[b];
@@ -810,7 +813,7 @@ int ensure_shard_cols(lx_index *h);
 // rows (events) whose branch belongs to each shard, at the current event count
 // (and every shard's column list)
 int ensure_shard_rows(lx_index *h) {
-    if (h->sc_events == h->n_events && h->sc_B == h->B) return 0;
+    if (h->sc_events == h->n_events && h->sc_gen == h->branch_gen) return 0;
     const uint32_t n = (uint32_t)h->n_events;
     const uint32_t G = h->shard_count;
     if (n > h->lay.sc_flag.cap() || h->lay.sc_rows.size() != G) {
@@ -836,13 +839,13 @@ int ensure_shard_rows(lx_index *h) {
     if (int rc = upload_cols(h)) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->sc_events = h->n_events;
-    h->sc_B = h->B;
+    h->sc_gen = h->branch_gen;
     return 0;
 }
 
 // the column lists alone (the incremental exchange lists its rows itself)
 int ensure_shard_cols(lx_index *h) {
-    if (h->lay.sc_cols && h->sc_cols_B == h->B) return 0;
+    if (h->lay.sc_cols && h->sc_cols_gen == h->branch_gen) return 0;
     if (int rc = upload_cols(h)) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return 0;
@@ -861,7 +864,7 @@ int upload_cols(lx_index *h) {
     HIPCHK(h, h->lay.sc_cols.renew(all.size(), h->stream, true));
     if (!all.empty())
         HIPCHK(h, hipMemcpyAsync(h->lay.sc_cols, all.data(), all.size() * 4, hipMemcpyHostToDevice, h->stream));
-    h->sc_cols_B = h->B;
+    h->sc_cols_gen = h->branch_gen;
     return 0;
 }
 
@@ -3328,6 +3331,7 @@ int lx_index_view(lx_index *h, IndexView *o) {
     o->n_events = h->n_events;
     o->V = h->V;
     o->B = h->B;
+    o->branch_gen = h->branch_gen;
     o->quorum = h->quorum;
     o->max_seq = h->max_seq;
     o->wpad = h->lay.wpad;

@@ -26,7 +26,8 @@ constexpr uint32_t kQiMaxV = 8192;
 struct lx_qi {
     lx_index *ix = nullptr;
     std::string err;
-    uint32_t V = 0, quorum = 0, B = 0;
+    uint32_t V = 0, quorum = 0;
+    uint64_t k_gen = 0;                    // branch_gen the cheater lists were built for; 0 = stale
     bool dirty = true;
     lxi::DevBuf<uint32_t> mt, sp, median, weights;
     lxi::DevBuf<int32_t> cheat_of;
@@ -81,7 +82,7 @@ int view(lx_qi *q, IndexView *iv) {
 
 // cheaters' branch lists: GetMergedHighestBefore gathers over BranchIDByCreators
 int refresh_cheaters(lx_qi *q, const IndexView &iv) {
-    if (q->B == iv.B) return 0;
+    if (q->k_gen == iv.branch_gen) return 0;
     std::vector<int32_t> of(q->V, -1);
     std::vector<uint32_t> off{0}, br;
     for (uint32_t c = 0; c < q->V; c++) {
@@ -97,7 +98,7 @@ int refresh_cheaters(lx_qi *q, const IndexView &iv) {
     if (!br.empty()) QHIP(q, hipMemcpyAsync(q->cheat_br, br.data(), br.size() * 4, hipMemcpyHostToDevice, iv.stream));
     QHIP(q, hipMemcpyAsync(q->cheat_of, of.data(), q->V * 4ull, hipMemcpyHostToDevice, iv.stream));
     QHIP(q, hipStreamSynchronize(iv.stream));
-    q->B = iv.B;
+    q->k_gen = iv.branch_gen;
     return 0;
 }
 
@@ -208,7 +209,7 @@ int lx_qi_reset(lx_qi *q) {
     QHIP(q, hipMemcpyAsync(q->weights, iv.weights->data(), V * 4, hipMemcpyHostToDevice, iv.stream));
     QHIP(q, hipStreamSynchronize(iv.stream));
     q->dirty = true;
-    q->B = 0;
+    q->k_gen = 0;
     return refresh_cheaters(q, iv);
 }
 

@@ -88,10 +88,10 @@ struct FcCache {
     // tile fills: partial sums and the cheaters' branch columns (k_root_fc)
     DU32 d_psum;
     DU32 d_k;                                        // kcol | kflag | kw, k_cap entries each
-    // k_B: the branch count the columns were built for; 0 = stale.  A drop can
-    // remove one creator's fork branch and a later Add give the same branch
-    // number to another creator's fork, so every DropNotFlushed clears it
-    uint32_t n_k = 0, k_B = 0, k_cap = 0;
+    // k_gen: the generation of the branch -> creator map (lx_index::branch_gen)
+    // the columns were built for; 0 = stale
+    uint32_t n_k = 0, k_cap = 0;
+    uint64_t k_gen = 0;
     lx_fc_stats st{};
 
     uint32_t find(uint32_t e) const { return e < slot_of.size() ? slot_of[e] : LX_NONE; }
@@ -163,7 +163,6 @@ struct FcCache {
         used = 0;
         hand = 0;
         last_a = last_sa = LX_NONE;
-        k_B = 0;
     }
 };
 
@@ -209,7 +208,7 @@ int fcc_make(lx_index *h) {
 
 // the cheaters' branch columns for k_root_fc, grouped by creator, original first
 int fcc_cheaters(lx_index *h, FcCache *c) {
-    if (c->k_B == h->B) return 0;
+    if (c->k_gen == h->branch_gen) return 0;
     std::vector<uint32_t> col, flag, kw;
     for (uint32_t v = 0; v < h->V; v++) {
         const auto &l = h->by_creator[v];
@@ -234,7 +233,7 @@ int fcc_cheaters(lx_index *h, FcCache *c) {
         HIPCHK(h, hipMemcpyAsync(c->d_k, all.data(), 4ull * all.size(), hipMemcpyHostToDevice, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
     }
-    c->k_B = h->B;
+    c->k_gen = h->branch_gen;
     return 0;
 }
 
@@ -482,7 +481,6 @@ void fcc_forget_from(lx_index *h, uint64_t n) {
     (void)fcc_quiesce(h, c);
     for (uint32_t s = 0; s < c->used; s++)
         if (c->ev[s] != LX_NONE && c->ev[s] >= n) c->free_slot(s);
-    c->k_B = 0;   // the branch -> creator map may change under the same B
 }
 
 extern "C" {

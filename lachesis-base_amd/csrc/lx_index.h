@@ -148,6 +148,13 @@ struct lx_index {
     // host mirror of BranchesInfo (creator / first seq per branch; by creator)
     std::vector<uint32_t> h_branch_creator, h_branch_first;
     std::vector<std::vector<uint32_t>> by_creator;
+    // generation of the branch -> creator map, never 0 once an epoch exists:
+    // bumped whenever the map changes (rebuild_columns: Reset, an Add that
+    // creates forks, a DropNotFlushed that removes them, lx_load_finish).  A
+    // drop can take a fork's branch number back and a later Add give it to
+    // another creator's fork, so the branch count alone does not identify the
+    // map: every table built from it is keyed on this counter
+    uint64_t branch_gen = 0;
 
     // capacities
     uint64_t n_cap = 0;
@@ -173,9 +180,9 @@ struct lx_index {
 
     // column-shard exchange cache (lay.sc_*: rows per shard at sc_events)
     uint64_t sc_events = ~0ull;
-    uint32_t sc_B = 0;
+    uint64_t sc_gen = 0;                  // branch_gen the rows were listed for
     std::vector<uint32_t> sc_col_off;    // shard q's columns: sc_cols[sc_col_off[q] .. sc_col_off[q+1])
-    uint32_t sc_cols_B = 0;               // branch count sc_cols was built for
+    uint64_t sc_cols_gen = 0;             // branch_gen sc_cols was built for
     // incremental LowestAfter exchange (lay.sx_*)
     bool sx_full = true;                  // the next exchange sends whole blocks (reset, drop, load)
     bool sx_active = false;               // pack / unpack / lx_shard_block use the dirty lists

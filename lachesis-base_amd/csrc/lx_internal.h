@@ -825,6 +825,7 @@ struct IndexView {
     uint64_t stride;
     uint64_t n_events;
     uint32_t V, B, quorum;
+    uint64_t branch_gen;         // generation of the branch -> creator map (lx_index.h)
     uint32_t max_seq;            // largest seq indexed this epoch
     const uint32_t *wpad;
     const uint32_t *ev_branch;
