@@ -71,6 +71,9 @@ const char *lx_last_error(const lx_index *h);
  *                epochs where the 256 heaviest validators' stake alone can reach the quorum,
  *                a query reads more of its rows only while their count leaves it open;
  *                lx_fc_early_counters)
+ *   "fc_early_forks" 1: the early exit in fork epochs too (default 0; needs "fc_early" and
+ *                "fc_fk" on, 1..64 cheaters, more than 512 validators, a whole handle:
+ *                k_fc_fk_early, lx_fc_early_fork_rounds).  0: fork epochs read whole rows
  *   "cpw"        walker columns per workgroup: 0 (auto), 1, 2, 4, 8 or 12 (8, 12: packed
  *                fork-free epochs, else 4; 12: whole handles, a sharded one walks 8)
  *   "pack16"     0: two slot units per event even when every seq fits 16 bits
@@ -237,6 +240,20 @@ int lx_fc_cache_stats(const lx_index *h, lx_fc_stats *out);
  * (bench). */
 int lx_fc_early_rounds(lx_index *h, uint64_t out[4]);
 int lx_fc_early_counters(lx_index *h, uint64_t *queries, uint64_t *second_round, uint64_t *whole_rows);
+
+/* The early exit in fork epochs (option fc_early_forks, off by default) since
+ * the last call.  The path runs on launches of >= 2^14 queries over a whole
+ * handle (no column shard, no row-segment rank) in an epoch with 1..64
+ * cheaters (option fc_fk on), V >= 516 validators, fork branches that fit 32
+ * uint4 past column V & ~3, and whose validators 0..511 can reach the quorum
+ * alone.  It reads both rows in rounds of columns [0, 128) plus every fork
+ * branch, [128, 256), [256, 512) and the originals left, each only when the
+ * count so far leaves the quorum open.  out[0] queries that read round 2,
+ * out[1] round 3, out[2] EVERY query decided on the path, out[3] round 4 (the
+ * device counters' own order; lx_fc_early_rounds, which keeps counting the
+ * fork-free path only, puts the total first).  Synchronizes the handle's
+ * stream; resets the counts.  Diagnostics. */
+int lx_fc_early_fork_rounds(lx_index *h, uint64_t out[4]);
 
 /* Column-sharded partial: stake sum over this shard's creators, plus
  * 0x80000000 when this shard owns branch(b) and A observes it as forked.

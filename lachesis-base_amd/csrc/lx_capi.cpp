@@ -783,6 +783,43 @@ int lx_fc_args(lx_index *h, uint64_t n, const uint32_t *a, const uint32_t *b, ui
             f.early_full = h->d_fc_full;
         }
     }
+    // the same in fork epochs (k_fc_fk_early, option fc_early_forks): whole
+    // handles whose fork tables are valid (1..64 cheaters), more than 512
+    // original columns before the straddling uint4 (t0 > 128: round 4 has
+    // columns, as the gate above asks of fork-free rows) and every fork branch
+    // within one uint4 per lane of round 1.  rest[r]: every validator whose
+    // original column is unread after round r + 1, cheaters included
+    if (!partial && !h->sharded() && !h->rowseg() && h->B > h->V && h->fc_early && h->fc_early_forks && f.fk_hi4 &&
+        n >= kFcEarlyMinQueries && h->own_lo == 0 && h->own_hi == h->V) {
+        const uint32_t t0 = h->V / 4;
+        if (t0 > 128 && f.fk_hi4 >= t0 && f.fk_hi4 - t0 <= 32) {
+            uint64_t w512 = 0, r1 = 0, r2 = 0, r3 = 0;
+            for (uint32_t c = 0; c < 4 * t0; c++) {
+                const uint64_t wc = h->weights[c];
+                if (c < 512) w512 += wc;
+                if (c >= 128) r1 += wc;
+                if (c >= 256) r2 += wc;
+                if (c >= 512) r3 += wc;
+            }
+            if (w512 >= h->quorum && r1 <= 0xFFFFFFFFull) {
+                if (!h->d_fc_fke) {
+                    // zeroed and synchronized before any launch can count into it (as d_fc_full)
+                    DevBuf<unsigned long long> p;
+                    HIPCHK(h, p.renew(4));
+                    hipError_t e = hipMemsetAsync(p, 0, 32, h->stream);
+                    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+                    if (e != hipSuccess) return h->hip(e, "ForklessCause fork early-exit counters");
+                    h->d_fc_fke = std::move(p);
+                }
+                f.fke = 1;
+                f.fke_rest[0] = (uint32_t)r1;
+                f.fke_rest[1] = (uint32_t)r2;
+                f.fke_rest[2] = (uint32_t)r3;
+                f.fke_t0 = t0;
+                f.fke_full = h->d_fc_fke;
+            }
+        }
+    }
     h->fc_unchecked = true;   // a query it cannot answer flags status[1]; lx_sync reports it
     *fa = f;
     return 0;
@@ -1625,6 +1662,20 @@ int lx_fc_early_rounds(lx_index *h, uint64_t out[4]) {
     return 0;
 }
 
+int lx_fc_early_fork_rounds(lx_index *h, uint64_t out[4]) {
+    if (!h || !out) return LX_ERR_ARG;
+    HIPCHK(h, set_dev(h->device));
+    uint64_t c[4] = {0, 0, 0, 0};
+    if (h->d_fc_fke) {
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        HIPCHK(h, hipMemcpy(c, h->d_fc_fke, 32, hipMemcpyDeviceToHost));
+        HIPCHK(h, hipMemsetAsync(h->d_fc_fke, 0, 32, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    for (int i = 0; i < 4; i++) out[i] = c[i];   // past round 1, past round 2, every query, past round 3
+    return 0;
+}
+
 int lx_fc_early_counters(lx_index *h, uint64_t *queries, uint64_t *second_round, uint64_t *whole_rows) {
     if (!queries || !second_round || !whole_rows) return LX_ERR_ARG;
     uint64_t r[4];
@@ -1646,6 +1697,9 @@ int lx_set_option(lx_index *h, const char *name, int64_t value) {
         h->fc_fk = value != 0;
     } else if (k == "fc_early") {
         h->fc_early = value != 0;
+    } else if (k == "fc_early_forks") {
+        if (value != 0 && value != 1) return h->fail(LX_ERR_ARG, "fc_early_forks must be 0 or 1");
+        h->fc_early_forks = value != 0;
     } else if (k == "fc_early_lanes") {
         if (value != 16 && value != 32) return h->fail(LX_ERR_ARG, "fc_early_lanes must be 16 or 32");
         h->fc_early_lanes = (uint32_t)value;

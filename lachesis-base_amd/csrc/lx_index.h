@@ -280,6 +280,8 @@ struct lx_index {
     lxi::DBytes fcs_tmp;
     size_t fcs_tmp_bytes = 0;              // of it, what the scan asks for
     lxi::DevBuf<unsigned long long> d_fc_full;   // early exit counters (device): past round 1, past round 2, all
+    bool fc_early_forks = false;           // option fc_early_forks=1: the early exit in fork epochs too (k_fc_fk_early)
+    lxi::DevBuf<unsigned long long> d_fc_fke;    // ... its counters, same layout
     bool seg_auto = true;                  // option seg_auto=0: never split a batch on its own
     uint32_t n_cus = 256;                  // compute units of the device (auto segments)
     std::vector<hipEvent_t> seg_ev;

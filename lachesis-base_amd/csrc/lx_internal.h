@@ -250,6 +250,14 @@ struct FcArgs {
     const uint32_t *fk_c;
     const uint32_t *fk_wch;
     uint32_t fk_hi4;
+    // early exit in fork epochs (k_fc_fk_early; fke = 0: off): the weight of
+    // every validator whose original column lies past uint4 32, 64 and 128 of
+    // the row (below t0 = V / 4: the straddling uint4 and the fork branches
+    // [t0, fk_hi4) are read in round 1)
+    uint32_t fke_rest[3];
+    uint32_t fke_t0;
+    unsigned long long *fke_full;     // counters, laid out as early_full
+    uint32_t fke;
 };
 constexpr uint32_t kFcFkMaxCheaters = 64;   // one 64-bit mask per query
 constexpr uint64_t kFcEarlyMinQueries = 1u << 14;   // launches this large take the early exit (k_fc_early)

@@ -2019,6 +2019,221 @@ __global__ __launch_bounds__(256) void k_fc_fk(FcArgs a) {
     }
 }
 
+// The early exit in fork epochs (options fc_early and fc_early_forks; whole
+// handles, <= 64 cheaters, more than 512 validators, a fork tail of <= 32
+// uint4): k_fc_early's rounds over k_fc_fk's tables.  In uint4 indices of the
+// row, with t0 = V / 4 and fk_hi4 the end of the fork tables:
+//   round 1  [0, 32) and [t0, fk_hi4): the 128 first originals and EVERY fork
+//            branch (plus the originals of the straddling uint4 when V % 4 != 0)
+//   round 2  [32, 64)     round 3  [64, 128)     round 4  [128, t0)
+// No column is read twice, and after round 1 a cheater can still turn up only
+// through its original column.  The running count is the weight of the
+// counting non-cheater originals read so far plus the weight of every cheater
+// whose mask bit has appeared so far -- each added once, in the round its bit
+// first shows (`added`) -- so it only grows; fke_rest[r] is the weight of
+// every validator whose original column is still unread after round r + 1 (a
+// cheater already counted through a fork branch is in it again: the bound is
+// looser, never wrong).  count <= final count <= count + rest, and the
+// reference compares only the final count with the quorum
+// (vecfc/forkless_cause.go:63-82, inter/pos/stake.go:47-55): count >= quorum
+// answers true, count + rest < quorum false, else the next round is read.  The
+// early false (forkless_cause.go:49-54) answers 0 after round 1.  Counters
+// (fke_full): [0] queries past round 1, [1] past round 2, [2] every query of
+// this kernel, [3] past round 3.
+// (32-bit mask: 96 VGPRs, a fifth wave per SIMD, without scratch; the 64-bit one would spill)
+template <typename M>   // M: the cheater mask, uint32_t (<= 32 cheaters) or uint64_t
+__global__ __launch_bounds__(256, sizeof(M) == 4 ? 5 : 4) void k_fc_fk_early(FcArgs a) {
+    constexpr uint32_t MB = 8 * sizeof(M);
+    constexpr int L = 32;
+    constexpr int kW = (int)MB / L;
+    const int lane = threadIdx.x % L;
+    const uint64_t qpb = 256 / L;
+    const uint32_t t0 = a.fke_t0;                 // > 128, fk_hi4 - t0 <= 32 (lx_fc_args)
+    const uint32_t it = t0 + lane;                // this lane's uint4 of the tail
+    const bool tail = it < a.fk_hi4;
+    const uint4 *wv = reinterpret_cast<const uint4 *>(a.fk_w);
+    const uint4 *cv = reinterpret_cast<const uint4 *>(a.fk_c);
+    auto cbit = [](uint32_t k) -> M { return k < MB ? ((M)1 << k) : (M)0; };
+    // round 1's weights and cheater bits stay in registers: uint4 lane and t0 + lane
+    uint4 wr[2];
+    M cm[2][4];
+#pragma unroll
+    for (int t = 0; t < 2; t++) {
+        const bool in = t ? tail : true;
+        const uint32_t i = t ? it : (uint32_t)lane;
+        wr[t] = in ? wv[i] : make_uint4(0, 0, 0, 0);
+        const uint4 c = in ? cv[i] : make_uint4(LX_NONE, LX_NONE, LX_NONE, LX_NONE);
+        cm[t][0] = cbit(c.x); cm[t][1] = cbit(c.y); cm[t][2] = cbit(c.z); cm[t][3] = cbit(c.w);
+    }
+    // this lane's share of the cheaters' weights: cheater lane + t * L
+    uint32_t wch[kW];
+#pragma unroll
+    for (int t = 0; t < kW; t++) {
+        const uint32_t k = lane + t * L;
+        wch[t] = k < a.n_cheat ? a.fk_wch[k] : 0u;
+    }
+    // one uint4 of both rows: the non-cheater originals' weight and the cheaters' bits that count
+    auto terms = [](const u4v &l, const u4v &h, const uint4 &w, const M (&cb)[4], uint32_t &s, M &m) {
+        const uint32_t hh[4] = {h.x, h.y, h.z, h.w};
+        const uint32_t ll[4] = {l.x, l.y, l.z, l.w};
+        const uint32_t ww[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+        for (int c = 0; c < 4; c++) {
+            const bool on = fc_term(ll[c], hh[c], 1u, true) != 0;
+            s += on ? ww[c] : 0u;
+            m |= on ? cb[c] : (M)0;
+        }
+    };
+    // ... of a later round: weights and cheater indices from the tables
+    auto terms_at = [&](const u4v *ha, const u4v *lb, uint32_t i, uint32_t &s, M &m) {
+        const u4v hh = __builtin_nontemporal_load(ha + i);
+        const u4v ll = __builtin_nontemporal_load(lb + i);
+        const uint4 cc = cv[i];
+        const M cb[4] = {cbit(cc.x), cbit(cc.y), cbit(cc.z), cbit(cc.w)};
+        terms(ll, hh, wv[i], cb, s, m);
+    };
+    // the end of a round: the mask OR-reduced over the query's lanes, each lane
+    // adds the weights of its share of the cheaters that are new in it, and the
+    // round's sum over the lanes
+    auto settle = [&](uint32_t s, M m, M &added) -> uint32_t {
+        if constexpr (MB == 64) {
+            uint32_t mlo = (uint32_t)m, mhi = (uint32_t)((uint64_t)m >> 32);
+#pragma unroll
+            for (int off = L / 2; off > 0; off >>= 1) {
+                mlo |= __shfl_xor(mlo, off, L);
+                mhi |= __shfl_xor(mhi, off, L);
+            }
+            m = (M)(((uint64_t)mhi << 32) | mlo);
+        } else {
+#pragma unroll
+            for (int off = L / 2; off > 0; off >>= 1) m |= (M)__shfl_xor((uint32_t)m, off, L);
+        }
+        const M fresh = m & ~added;
+        added |= fresh;
+#pragma unroll
+        for (int t = 0; t < kW; t++) s += ((fresh >> (lane + t * L)) & 1u) ? wch[t] : 0u;
+#pragma unroll
+        for (int off = L / 2; off > 0; off >>= 1) s += __shfl_xor(s, off, L);
+        return s;
+    };
+    uint32_t n1 = 0, n2 = 0, n3 = 0, ne = 0;
+    const uint64_t step = (uint64_t)gridDim.x * qpb;
+    uint64_t q = blockIdx.x * qpb + threadIdx.x / L;
+    // Three queries of a half-wave are under way, each a stage further: the
+    // pair as asked (two ahead), the pair checked with branch(b) and
+    // creator(b) on lane 0 (one ahead), round 1 of both rows with
+    // HB(a)[branch(b)] (this one).  Every load an iteration consumes was
+    // issued an iteration earlier, all of an iteration's loads are issued
+    // together, and this query's round 1 is consumed first, so the next
+    // query's rows land in the same registers.
+    uint32_t A = 0, Bq = 0, hm = 0;
+    bool bad = false;
+    u4v hv = {0, 0, 0, 0}, lv = {0, 0, 0, 0}, ht = {0, 0, 0, 0}, lt = {0, 0, 0, 0};
+    uint32_t A1 = 0, B1 = 0, eb1 = 0, ec1 = LX_NONE, A2 = 0, B2 = 0;
+    bool bad1 = false;
+    auto ask = [&](uint64_t qq, uint32_t &A_, uint32_t &B_) {
+        A_ = a.qa_bcast ? a.qa_imm : a.qa[qq];
+        B_ = a.qb[qq];
+    };
+    auto check = [&](uint32_t &A_, uint32_t &B_, bool &bad_, uint32_t &eb, uint32_t &ec) {
+        bad_ = fc_bad(a, A_, B_);
+        if (bad_) { A_ = a.ev_lo; B_ = a.ev_lo; }
+        eb = 0;
+        ec = LX_NONE;
+        if (lane == 0) {
+            eb = a.ev_branch[B_];
+            ec = a.ev_creator[B_];
+        }
+    };
+    // round 1 (and, lane 0, HB(a)[branch(b)] of an own creator for the early false)
+    auto rows = [&](uint32_t A_, uint32_t B_, uint32_t eb, uint32_t ec, uint32_t &hm_, u4v &h_, u4v &l_, u4v &ht_,
+                    u4v &lt_) {
+        const u4v *ha = reinterpret_cast<const u4v *>(a.hb + (uint64_t)A_ * a.stride);
+        const u4v *lb = reinterpret_cast<const u4v *>(a.la + (uint64_t)B_ * a.stride);
+        h_ = __builtin_nontemporal_load(ha + lane);
+        l_ = __builtin_nontemporal_load(lb + lane);
+        ht_ = lt_ = u4v{0, 0, 0, 0};
+        if (tail) {
+            ht_ = __builtin_nontemporal_load(ha + it);
+            lt_ = __builtin_nontemporal_load(lb + it);
+        }
+        hm_ = 0;
+        if (lane == 0 && ec >= a.own_lo && ec < a.own_hi) hm_ = a.hb[(uint64_t)A_ * a.stride + eb];
+    };
+    if (q < a.n) {
+        ask(q, A, Bq);
+        check(A, Bq, bad, eb1, ec1);
+        rows(A, Bq, eb1, ec1, hm, hv, lv, ht, lt);
+    }
+    if (q + step < a.n) {
+        ask(q + step, A1, B1);
+        check(A1, B1, bad1, eb1, ec1);
+    }
+    if (q + 2 * step < a.n) ask(q + 2 * step, A2, B2);
+    for (; q < a.n; q += step) {
+        M added = 0, m = 0;
+        uint32_t s = 0;
+        terms(lv, hv, wr[0], cm[0], s, m);
+        terms(lt, ht, wr[1], cm[1], s, m);
+        const uint32_t A0 = A, B0 = Bq;
+        const bool bad0 = bad;
+        const bool early = __shfl((uint32_t)((hm & LX_MARK) != 0), 0, L) != 0;
+        // the stages move up
+        if (q + step < a.n) rows(A1, B1, eb1, ec1, hm, hv, lv, ht, lt);
+        A = A1; Bq = B1; bad = bad1;
+        if (q + 2 * step < a.n) {
+            A1 = A2; B1 = B2;
+            check(A1, B1, bad1, eb1, ec1);
+        }
+        if (q + 3 * step < a.n) ask(q + 3 * step, A2, B2);
+        uint32_t sum = settle(s, m, added);
+        if (!early && sum < a.quorum && sum + a.fke_rest[0] >= a.quorum) {
+            // round 2: uint4 [32, 64)
+            const u4v *ha = reinterpret_cast<const u4v *>(a.hb + (uint64_t)A0 * a.stride);
+            const u4v *lb = reinterpret_cast<const u4v *>(a.la + (uint64_t)B0 * a.stride);
+            s = 0; m = 0;
+            terms_at(ha, lb, lane + L, s, m);
+            sum += settle(s, m, added);
+            n1++;
+            if (sum < a.quorum && sum + a.fke_rest[1] >= a.quorum) {
+                // round 3: uint4 [64, 128), two per lane in flight
+                s = 0; m = 0;
+                terms_at(ha, lb, lane + 2 * L, s, m);
+                terms_at(ha, lb, lane + 3 * L, s, m);
+                sum += settle(s, m, added);
+                n2++;
+                if (sum < a.quorum && sum + a.fke_rest[2] >= a.quorum) {
+                    // round 4: the originals left, uint4 [128, t0)
+                    s = 0; m = 0;
+                    for (uint32_t i = lane + 4 * L; i < t0; i += L) terms_at(ha, lb, i, s, m);
+                    sum += settle(s, m, added);
+                    n3++;
+                }
+            }
+        }
+        if (lane == 0) {
+            const uint8_t r = bad0 ? 0xFF : (uint8_t)(!early && sum >= a.quorum);
+            a.out[q] = a.out_tag && !bad0 ? (uint8_t)(a.out_tag[q] << 1 | r) : r;
+            if (bad0) atomicOr(&a.status[1], 1u);
+        }
+        ne++;
+    }
+    if (a.fke_full && lane == 0 && ne) {
+        if (n1) atomicAdd(a.fke_full, (unsigned long long)n1);
+        if (n2) atomicAdd(a.fke_full + 1, (unsigned long long)n2);
+        atomicAdd(a.fke_full + 2, (unsigned long long)ne);
+        if (n3) atomicAdd(a.fke_full + 3, (unsigned long long)n3);
+    }
+}
+
+static hipError_t launch_fc_fk_early(const FcArgs &a, hipStream_t s) {
+    const uint64_t eb = std::min<uint64_t>((a.n + 7) / 8, 256 * 32);
+    if (!eb) return hipSuccess;
+    if (a.n_cheat <= 32) hipLaunchKernelGGL((k_fc_fk_early<uint32_t>), dim3((uint32_t)eb), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((k_fc_fk_early<uint64_t>), dim3((uint32_t)eb), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
 template <int LPQ>
 static hipError_t launch_fc_t(const FcArgs &a, bool forks, hipStream_t s) {
     const uint64_t qpb = 256 / LPQ;
@@ -2055,6 +2270,7 @@ static hipError_t launch_fc_early_t(const FcArgs &a, hipStream_t s) {
 hipError_t launch_fc(const FcArgs &a, uint32_t cols, bool forks, hipStream_t s) {
     if (forks && !a.fk_hi4 && !a.n_cheat) forks = false;   // no cheater among this handle's creators
     if (a.early && !forks) return a.early_lanes == 16 ? launch_fc_early_t<16>(a, s) : launch_fc_early_t<32>(a, s);
+    if (a.fke && forks && a.fk_hi4) return launch_fc_fk_early(a, s);
     const uint32_t nv = forks && a.fk_hi4 ? a.fk_hi4 : a.vhi4 - a.vlo4;
     // (rows of <= 8 branches: 2 lanes, twice the queries per wave -- C1's
     // 20-B rows 0.078 -> 0.072 ms per 2^22 queries, profiles/r04/fc_small_rows_r04y.jsonl)

@@ -56,6 +56,7 @@ SIGNATURES = [
     ("lx_get_server_stats", ctypes.c_int, [vp, u64p]),
     ("lx_live_handles", ctypes.c_int, []),
     ("lx_fc_early_rounds", ctypes.c_int, [vp, u64p]),
+    ("lx_fc_early_fork_rounds", ctypes.c_int, [vp, u64p]),
     ("lx_device_bytes", ctypes.c_int, [vp, u64p]),
     ("lx_get_rows_dev", ctypes.c_int, [vp, ctypes.c_uint32, ctypes.c_uint32, vp, vp, ctypes.c_uint64, vp]),
     ("lx_row_bytes_max", ctypes.c_int, [vp, u64p]),
@@ -395,6 +396,14 @@ class Index:
         the rest) since the last call (lx_fc_early_rounds)."""
         out = np.zeros(4, dtype=np.uint64)
         self._chk(self.L.lx_fc_early_rounds(self.h, _p(out, u64p)))
+        return tuple(int(x) for x in out)
+
+    def fc_early_fork_rounds(self):
+        """The early exit in fork epochs (option fc_early_forks) since the last
+        call: (queries past round 1, past round 2, every query of the path,
+        past round 3) (lx_fc_early_fork_rounds)."""
+        out = np.zeros(4, dtype=np.uint64)
+        self._chk(self.L.lx_fc_early_fork_rounds(self.h, _p(out, u64p)))
         return tuple(int(x) for x in out)
 
     def fc_early_counters(self):
