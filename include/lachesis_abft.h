@@ -20,6 +20,9 @@
  * DropNotFlushed, Reset): do not add events to that index directly (the one
  * exception is the reload of a persisted epoch before lx_abft_restore).
  * One host thread per handle; callbacks must not call back into the handle.
+ * The lx_mt calls of lachesis_mediantime.h on the same index are the
+ * exception: they only read the index, so BeginBlock can ask the block's
+ * MedianTime(atropos) (lx_mt_median_time, lx_mt_merged_times, lx_mt_set_times).
  */
 #ifndef LACHESIS_ABFT_H
 #define LACHESIS_ABFT_H

@@ -1875,6 +1875,7 @@ int lx_reset(lx_index *h, uint32_t nv, const uint32_t *w) {
     HIPCHK(h, hipMemcpyAsync(h->lay.branch_creator, idx.data(), nv * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(h->lay.wpad, wp.data(), (uint64_t)h->stride * 4, hipMemcpyHostToDevice, h->stream));
     h->n_events = h->n_flushed = 0;
+    h->rolled_epoch();
     h->rs_state = 0;
     h->pcols_used = h->sharded() ? norig : nv;
     h->B = h->B_flushed = nv;
@@ -1978,6 +1979,7 @@ int lx_drop_not_flushed(lx_index *h) {
     HIPCHK(h, set_dev(h->device));
     h->wb_ready = false;
     if (h->n_events == h->n_flushed && h->B == h->B_flushed) return 0;
+    h->rolled_back(h->n_flushed);
     if (h->pend_n && h->n_flushed >= h->pend_bs) {
         // every dropped event is still in the pending run: it never reached the
         // device, so the rollback is host-only (Build = Add + DropNotFlushed
@@ -3062,6 +3064,7 @@ int lx_load_rows(lx_index *h, uint32_t n, const uint32_t *creator, const uint32_
     if (!h->loading) {
         if (h->n_events) return h->fail(LX_ERR_STATE, "lx_load_rows needs a freshly reset handle");
         h->loading = true;
+        h->rolled_epoch();   // what a handle keyed on dense indices held is not of this load
         h->ld_first.assign(h->V, 1);
         h->ld_last.assign(h->V, 0);
         h->ld_count.assign(h->V, 0);
@@ -3377,12 +3380,29 @@ int lx_index_view(lx_index *h, IndexView *o) {
         const int rc = flush_pending(h);   // abft and the emitter enqueue after the index's work
         if (rc) return rc;
     }
+    return lx_index_peek(h, o);
+}
+
+uint64_t lx_index_kept_since(const lx_index *h, uint64_t gen) {
+    if (gen < h->epoch_gen) return 0;
+    uint64_t keep = ~0ull;
+    for (uint64_t k = gen - h->epoch_gen; k < h->roll_keep.size(); k++) keep = std::min(keep, h->roll_keep[k]);
+    return keep;
+}
+
+int lx_index_peek(lx_index *h, IndexView *o) {
+    if (!h || !o) return LX_ERR_ARG;
+    WHOLE_INDEX(h);
+    if (!h->have_epoch) return h->fail(LX_ERR_STATE, "index has no epoch (lx_reset first)");
     o->stream = h->stream;
     o->device = h->device;
     o->hb = h->lay.hb;
     o->la = h->lay.la;
     o->stride = h->pstride;
     o->n_events = h->n_events;
+    o->n_flushed = h->n_flushed;
+    o->epoch_gen = h->epoch_gen;
+    o->roll_gen = h->roll_gen;
     o->V = h->V;
     o->B = h->B;
     o->branch_gen = h->branch_gen;
@@ -3391,6 +3411,12 @@ int lx_index_view(lx_index *h, IndexView *o) {
     o->wpad = h->lay.wpad;
     o->ev_branch = h->lay.ev_branch;
     o->ev_creator = h->lay.ev_creator;
+    o->brow = h->lay.brow;
+    o->branch_first = h->lay.branch_first;
+    o->s_cap = h->s_cap;
+    o->cheat_of = h->lay.cheat_of;
+    o->cheat_off = h->lay.cheat_off;
+    o->cheat_br = h->lay.cheat_br;
     o->weights = &h->weights;
     o->by_creator = &h->by_creator;
     o->shard_count = h->shard_count;

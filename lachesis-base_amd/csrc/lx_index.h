@@ -155,6 +155,22 @@ struct lx_index {
     // another creator's fork, so the branch count alone does not identify the
     // map: every table built from it is keyed on this counter
     uint64_t branch_gen = 0;
+    // Rollbacks of the dense indices, for handles that key tables of their own
+    // on them (lx_mediantime.cpp).  roll_gen counts every event that lets an
+    // index name another event: lx_reset and the start of a load (nothing is
+    // kept: they also set epoch_gen = roll_gen) and every lx_drop_not_flushed
+    // that dropped something; roll_keep[k] is the flushed count rollback
+    // epoch_gen + 1 + k kept (lx_index_kept_since)
+    uint64_t roll_gen = 0, epoch_gen = 0;
+    std::vector<uint64_t> roll_keep;
+    void rolled_epoch() {
+        epoch_gen = ++roll_gen;
+        roll_keep.clear();
+    }
+    void rolled_back(uint64_t keep) {
+        roll_gen++;
+        roll_keep.push_back(keep);
+    }
 
     // capacities
     uint64_t n_cap = 0;

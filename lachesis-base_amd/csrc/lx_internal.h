@@ -567,6 +567,33 @@ struct QiBatch {
     uint32_t iself;              // inline self flags, bit i
 };
 
+// ---- MedianTime (lx_mediantime.hip, lx_mediantime.cpp): the merged creation
+// times of an event and their stake-weighted median
+constexpr uint32_t kMtMaxV = 8192;
+constexpr uint32_t kMtThreads = 1024;  // k_mt's largest workgroup: kMtMaxV / kMtThreads entries per thread
+constexpr uint32_t kMtInline = 16;     // a query of so many events carries them in the kernel arguments
+struct MtArgs {
+    const uint32_t *hb;
+    uint64_t stride;
+    uint32_t V;
+    uint32_t forks;              // B > V: fork marks and cheaters' branches exist
+    const int32_t *cheat_of;     // creator -> cheater index (-1: one branch)
+    const uint32_t *cheat_off;   // CSR over all branches of each cheater (original first)
+    const uint32_t *cheat_br;
+    const uint32_t *weights;     // by validator idx
+    const uint32_t *brow;        // [branch][seq - first] -> event
+    const uint32_t *branch_first;
+    uint32_t s_cap;
+    const unsigned long long *times;   // creation time per dense event
+    uint64_t n_times;            // of them set: a lookup past them reads as 0
+    uint32_t n;                  // queried events (one workgroup each)
+    const uint32_t *ev;          // device; NULL: iev
+    uint32_t iev[kMtInline];
+    unsigned long long default_time;
+    unsigned long long *median;  // [n], or NULL
+    unsigned long long *merged;  // [n][V], or NULL
+};
+
 // ---- batched abft caller (lx_abft_kernels.hip, lx_abft.cpp)
 struct RootFcArgs {
     const uint32_t *hb;
@@ -801,6 +828,7 @@ hipError_t launch_qi_apply(const QiArgs &a, const QiBatch &b, hipStream_t s);
 hipError_t launch_qi_median(const QiArgs &a, hipStream_t s);
 hipError_t launch_qi_metric(const QiArgs &a, const uint32_t *ev, uint32_t n, uint32_t cap, unsigned long long *out,
                             hipStream_t s);
+hipError_t launch_mt(const MtArgs &a, hipStream_t s);
 uint32_t root_fc_splits(uint32_t n_cand, uint32_t n_roots, uint32_t ncols);
 hipError_t launch_root_fc(const RootFcArgs &a, bool forks, bool seq16, hipStream_t s);
 uint32_t root_fc_blocks(const RootFcArgs &a);
@@ -831,16 +859,30 @@ struct IndexView {
     int device;
     uint32_t *hb, *la;
     uint64_t stride;
-    uint64_t n_events;
+    uint64_t n_events, n_flushed;
+    uint64_t epoch_gen, roll_gen;   // rollbacks of the dense indices (lx_index.h; lx_index_kept_since)
     uint32_t V, B, quorum;
     uint64_t branch_gen;         // generation of the branch -> creator map (lx_index.h)
     uint32_t max_seq;            // largest seq indexed this epoch
     const uint32_t *wpad;
     const uint32_t *ev_branch;
     const uint32_t *ev_creator;
+    const uint32_t *brow;        // [branch * s_cap + seq - branch_first[branch]] -> event
+    const uint32_t *branch_first;
+    uint32_t s_cap;
+    const int32_t *cheat_of;     // creator -> cheater index (-1: one branch); CSR over all
+    const uint32_t *cheat_off;   // branches of each cheater, original first (as GetArgs)
+    const uint32_t *cheat_br;
     const std::vector<uint32_t> *weights;
     const std::vector<std::vector<uint32_t>> *by_creator;
     uint32_t shard_count;
     bool loading;                // between lx_load_rows and lx_load_finish
 };
 int lx_index_view(lx_index *h, IndexView *out);
+// the same without launching the pending run of small batches: n_events counts
+// it, the device tables may not hold it yet.  For callers that enqueue nothing
+// that reads those events' rows
+int lx_index_peek(lx_index *h, IndexView *out);
+// events that kept their dense index through every rollback after generation
+// `gen` (a roll_gen seen earlier): the smallest flushed count any of them left
+uint64_t lx_index_kept_since(const lx_index *h, uint64_t gen);

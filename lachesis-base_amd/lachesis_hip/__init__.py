@@ -15,6 +15,8 @@ vecfc/forkless_cause_test.go:
 * :mod:`batcher`      -- level-synchronous DAG batcher (include/lachesis_batcher.h):
   parents-first buffering, bulk release in topological levels
 * :mod:`emitter`      -- emitter/ancestor.QuorumIndexer over include/lachesis_emitter.h
+* :mod:`mediantime`   -- vecmt's MedianTime / merged HighestBeforeTime over
+  include/lachesis_mediantime.h (:class:`MedianTimeIndex`)
 * :mod:`abft`         -- abft.IndexedLachesis over include/lachesis_abft.h:
   frames, roots, election, blocks with batched ForklessCause on the GPU
 
@@ -29,3 +31,5 @@ from . import tools  # noqa: F401
 from . import abft  # noqa: F401
 from . import emitter  # noqa: F401
 from . import batcher  # noqa: F401
+from . import mediantime  # noqa: F401
+from .mediantime import MedianTimeIndex  # noqa: F401

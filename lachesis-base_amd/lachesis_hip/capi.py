@@ -140,6 +140,15 @@ SIGNATURES = [
     ("lx_qi_matrix", ctypes.c_int, [vp, u32p]),
     ("lx_qi_self_parent_seqs", ctypes.c_int, [vp, u32p]),
     ("lx_qi_metric_of", ctypes.c_int, [vp, ctypes.c_uint32, u32p, ctypes.c_uint32, u64p]),
+    # include/lachesis_mediantime.h
+    ("lx_mt_create", ctypes.c_int, [vp, ctypes.POINTER(vp)]),
+    ("lx_mt_destroy", None, [vp]),
+    ("lx_mt_last_error", ctypes.c_char_p, [vp]),
+    ("lx_mt_reset", ctypes.c_int, [vp]),
+    ("lx_mt_set_times", ctypes.c_int, [vp, ctypes.c_uint64, ctypes.c_uint64, u64p]),
+    ("lx_mt_num_times", ctypes.c_uint64, [vp]),
+    ("lx_mt_median_time", ctypes.c_int, [vp, ctypes.c_uint32, u32p, ctypes.c_uint64, u64p]),
+    ("lx_mt_merged_times", ctypes.c_int, [vp, ctypes.c_uint32, u32p, u64p]),
     # include/lachesis_batcher.h
     ("lx_batcher_create", ctypes.c_int, [ctypes.POINTER(vp)]),
     ("lx_batcher_destroy", None, [vp]),
