@@ -3410,6 +3410,7 @@ int lx_index_peek(lx_index *h, IndexView *o) {
     o->max_seq = h->max_seq;
     o->wpad = h->lay.wpad;
     o->ev_branch = h->lay.ev_branch;
+    o->ev_seq = h->lay.ev_seq;
     o->ev_creator = h->lay.ev_creator;
     o->brow = h->lay.brow;
     o->branch_first = h->lay.branch_first;

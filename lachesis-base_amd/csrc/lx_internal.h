@@ -594,6 +594,46 @@ struct MtArgs {
     unsigned long long *merged;  // [n][V], or NULL
 };
 
+// ---- ancestry (lx_ancestry.hip, lx_ancestry.cpp): "x is head or an ancestor
+// of head" from the planes, and the sets of unlabelled ancestors blocks confirm
+constexpr uint32_t kAncMaxHeads = 16;          // heads of one confirm launch
+constexpr uint32_t kAncLdsBytes = 64 * 1024;   // their HighestBefore rows in LDS (of 160 KiB per CU)
+constexpr uint32_t kAncThreads = 256;
+constexpr uint32_t kAncNoHead = 0xFFu;         // AncArgs::win: the launch gave the event no label
+struct AncPairArgs {
+    const uint32_t *hb, *la;
+    uint64_t stride;
+    const uint32_t *ev_branch, *ev_seq;
+    const uint32_t *head, *x;    // [n]
+    uint64_t n;
+    uint8_t *out;                // [n]
+};
+// One confirm launch: H heads in call order over the events [lo, hi), per_wg
+// of them per workgroup (a multiple of kAncThreads), n_wg workgroups.
+//   cnt[0]                : events the call's earlier launches labelled
+//   cnt[1 + k * n_wg + w] : events of workgroup w that take head k's label
+//   cnt[1 + H * n_wg]     : 0
+//   off                   : the exclusive prefix sums of cnt
+struct AncArgs {
+    const uint32_t *hb, *la;
+    uint64_t stride;
+    uint32_t B;
+    uint32_t row_words;          // LDS words per staged row (B, or B rounded up to 4 when rows are read as uint4)
+    const uint32_t *ev_branch, *ev_seq;
+    uint32_t *labels;            // [dense event]; valid below hi
+    uint32_t lo, hi;
+    uint32_t per_wg, n_wg;
+    uint32_t H;
+    uint32_t head[kAncMaxHeads], label[kAncMaxHeads];
+    uint32_t top;                // the highest of the heads: no event above it is asked
+    uint8_t *win;                // [hi - lo]: the head (0 .. H-1) whose label the event takes, or kAncNoHead
+    uint32_t *cnt, *off;
+    uint32_t *low;               // atomicMin: the lowest event of [lo, hi) left without a label
+    uint32_t *out_ev;            // the call's labelled events, grouped by head
+    uint32_t out_cap;
+    uint32_t *n_new;             // [H] of this launch
+};
+
 // ---- batched abft caller (lx_abft_kernels.hip, lx_abft.cpp)
 struct RootFcArgs {
     const uint32_t *hb;
@@ -829,6 +869,11 @@ hipError_t launch_qi_median(const QiArgs &a, hipStream_t s);
 hipError_t launch_qi_metric(const QiArgs &a, const uint32_t *ev, uint32_t n, uint32_t cap, unsigned long long *out,
                             hipStream_t s);
 hipError_t launch_mt(const MtArgs &a, hipStream_t s);
+hipError_t launch_anc_pairs(const AncPairArgs &a, hipStream_t s);
+hipError_t anc_scan_bytes(uint32_t n, size_t *bytes);
+// count, scan and scatter of one confirm launch (lx_ancestry.hip)
+hipError_t launch_anc_confirm(const AncArgs &a, void *tmp, size_t tmp_bytes, hipStream_t s);
+hipError_t launch_anc_low(const uint32_t *labels, uint32_t lo, uint32_t hi, uint32_t *low, hipStream_t s);
 uint32_t root_fc_splits(uint32_t n_cand, uint32_t n_roots, uint32_t ncols);
 hipError_t launch_root_fc(const RootFcArgs &a, bool forks, bool seq16, hipStream_t s);
 uint32_t root_fc_blocks(const RootFcArgs &a);
@@ -866,6 +911,7 @@ struct IndexView {
     uint32_t max_seq;            // largest seq indexed this epoch
     const uint32_t *wpad;
     const uint32_t *ev_branch;
+    const uint32_t *ev_seq;
     const uint32_t *ev_creator;
     const uint32_t *brow;        // [branch * s_cap + seq - branch_first[branch]] -> event
     const uint32_t *branch_first;

@@ -17,6 +17,8 @@ vecfc/forkless_cause_test.go:
 * :mod:`emitter`      -- emitter/ancestor.QuorumIndexer over include/lachesis_emitter.h
 * :mod:`mediantime`   -- vecmt's MedianTime / merged HighestBeforeTime over
   include/lachesis_mediantime.h (:class:`MedianTimeIndex`)
+* :mod:`ancestry`     -- DfsSubgraph / confirmEvents as scans of the vector clock
+  over include/lachesis_ancestry.h (:class:`AncestryIndex`)
 * :mod:`abft`         -- abft.IndexedLachesis over include/lachesis_abft.h:
   frames, roots, election, blocks with batched ForklessCause on the GPU
 
@@ -33,3 +35,5 @@ from . import emitter  # noqa: F401
 from . import batcher  # noqa: F401
 from . import mediantime  # noqa: F401
 from .mediantime import MedianTimeIndex  # noqa: F401
+from . import ancestry  # noqa: F401
+from .ancestry import AncestryIndex  # noqa: F401

@@ -149,6 +149,17 @@ SIGNATURES = [
     ("lx_mt_num_times", ctypes.c_uint64, [vp]),
     ("lx_mt_median_time", ctypes.c_int, [vp, ctypes.c_uint32, u32p, ctypes.c_uint64, u64p]),
     ("lx_mt_merged_times", ctypes.c_int, [vp, ctypes.c_uint32, u32p, u64p]),
+    # include/lachesis_ancestry.h
+    ("lx_anc_create", ctypes.c_int, [vp, ctypes.POINTER(vp)]),
+    ("lx_anc_destroy", None, [vp]),
+    ("lx_anc_last_error", ctypes.c_char_p, [vp]),
+    ("lx_anc_reset", ctypes.c_int, [vp]),
+    ("lx_anc_observes", ctypes.c_int, [vp, ctypes.c_uint64, u32p, u32p, u8p]),
+    ("lx_anc_confirm", ctypes.c_int, [vp, ctypes.c_uint32, u32p, u32p, u32p]),
+    ("lx_anc_last_confirmed", ctypes.c_int, [vp, u32p, ctypes.c_uint64, u64p]),
+    ("lx_anc_labels", ctypes.c_int, [vp, ctypes.c_uint64, ctypes.c_uint64, u32p]),
+    ("lx_anc_set_labels", ctypes.c_int, [vp, ctypes.c_uint64, ctypes.c_uint64, u32p]),
+    ("lx_anc_low_water", ctypes.c_int, [vp, u64p]),
     # include/lachesis_batcher.h
     ("lx_batcher_create", ctypes.c_int, [ctypes.POINTER(vp)]),
     ("lx_batcher_destroy", None, [vp]),
