@@ -187,9 +187,49 @@ int lx_abft_block_log(const lx_abft *a, uint32_t *n_blocks, const uint32_t **fra
                       const uint32_t **confirmed);
 
 /* IndexedLachesis.Build (indexed_lachesis.go:53-63): frame of a self-emitted
- * event (added, evaluated, then dropped again). */
+ * event (added, evaluated, then dropped again).  The drop is a rollback of the
+ * index: handles that follow rollbacks react (lachesis_mediantime.h,
+ * lachesis_ancestry.h).  lx_abft_build_frames below answers without it; this
+ * call remains the one for a candidate that would open a new branch. */
 int lx_abft_build(lx_abft *a, uint32_t creator_idx, uint32_t seq, uint32_t n_parents, const uint32_t *parents,
                   uint32_t *out_frame);
+
+/* Orderer.Build (abft/event_processing.go:15-30, calcFrameIdx :163-189 with
+ * checkOnly = false) for n candidate events that are NOT added: each is judged
+ * alone against the current epoch, candidates never see each other.
+ * parent_off / parent_idx as lx_add_batch (dense indices of existing events,
+ * self-parent first).  out_frame[i] is what lx_abft_build would return for
+ * candidate i; out_is_root[i] (optional) = frame != selfParentFrame.
+ * Reads only: no event is added, no rollback counted, no root slot, no
+ * callback, no election.  Handles that follow rollbacks of the index (lx_mt,
+ * lx_anc, the pending small-batch run's tables) keep what they hold; the stats
+ * of lx_abft_last_stats stay those of the last lx_abft_process_batch.
+ *
+ * All input is checked before any device work; *err_index (optional) receives
+ * the first offending candidate.  LX_ERR_STATE: the handle is not
+ * bootstrapped.  LX_ERR_ARG: creator >= V; seq == 0; a parent >=
+ * lx_num_events; a duplicate parent; seq > 1 without a first parent of the
+ * same creator at seq - 1; seq == 1 with a first parent of the same creator;
+ * or a candidate that would open a new branch -- its self-parent is not the
+ * last event of its branch, or seq == 1 while the creator already has events
+ * (fillGlobalBranchID, vecengine/index.go:105-141, would append a branch).
+ * lx_abft_build remains the call for that case.  A candidate may extend any
+ * existing branch tip, a cheater's fork branch included.  n == 0 is ok and
+ * launches nothing. */
+int lx_abft_build_frames(lx_abft *a, uint32_t n, const uint32_t *creator_idx, const uint32_t *seq,
+                         const uint64_t *parent_off, const uint32_t *parent_idx,
+                         uint32_t *out_frame, uint8_t *out_is_root, uint32_t *err_index);
+
+/* GPU work of the last lx_abft_build_frames (zeros after a call that failed
+ * its input checks or had n == 0). */
+typedef struct lx_abft_build_stats {
+    uint32_t launches;      /* kernel launches: uploads, k_build_rows, root-FC and quorum per round */
+    uint32_t frame_steps;   /* (frame, round) steps evaluated */
+    uint32_t rounds;        /* waits: one per round of the frame loop */
+    uint32_t fc16;          /* 1: the packed 16-bit root-FC kernel ran */
+    uint64_t fc_pairs;      /* (candidate, root) pairs evaluated */
+} lx_abft_build_stats;
+int lx_abft_build_last_stats(const lx_abft *a, lx_abft_build_stats *out);
 
 uint32_t lx_abft_epoch(const lx_abft *a);
 uint32_t lx_abft_last_decided_frame(const lx_abft *a);

@@ -44,7 +44,8 @@
  *   - lx_drop_not_flushed that dropped events (directly, or inside the abft
  *     handle): dense indices at or above the flushed count name other events
  *     afterwards, so every label at or above it is gone, the low-water mark is
- *     clamped to it and lx_anc_last_confirmed is empty.
+ *     clamped to it and lx_anc_last_confirmed is empty.  lx_abft_build_frames
+ *     does not roll back (lx_abft_build does): the labels stay.
  * Nothing is persisted: after a restart the caller hands the stored table
  * back with lx_anc_set_labels.
  *

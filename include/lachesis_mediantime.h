@@ -40,7 +40,9 @@
  *     handle: lx_abft_build, a wrong claimed frame): dense indices at or above
  *     the flushed count name other events afterwards, so every time at or
  *     above it is forgotten, whether it was set ahead of Add or not.  Set them
- *     again with the events added in their place.
+ *     again with the events added in their place.  lx_abft_build_frames asks
+ *     the same question without adding the event: it does not roll back, and
+ *     times set ahead stay.
  * Nothing about times is persisted: after a restart (lx_load_rows /
  * lx_load_finish) the caller sets the times of the loaded events again.
  *

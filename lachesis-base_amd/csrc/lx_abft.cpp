@@ -237,6 +237,12 @@ struct lx_abft {
     DVec<VoteArgs> ea_args;               // ... launch args, grouped by round
     DVec<RootFcArgs> d_fcargs;            // merged frame steps of a claimed batch: per-step args
     DVec<QuorumArgs> d_qargs;
+    // lx_abft_build_frames: the scratch plane of virtual rows, the per-candidate
+    // tables, bit rows nobody reads, the NONE list k_root_quorum takes as events
+    DVec<uint32_t> b_plane, b_tab, b_bits, b_none;
+    DVec<BuildArgs> b_args;             // the tables' pointers as the OWN kernels read them
+    uint64_t b_none_n = 0;              // entries of b_none written
+    lx_abft_build_stats bstats{};
     uint32_t n_k = 0;
     uint64_t k_gen = 0;                 // branch_gen the cheater columns were built for; 0 = stale
     std::vector<uint32_t> h_row;
@@ -637,9 +643,24 @@ struct FcStep {
     uint64_t row0, qoff;
 };
 
+// lx_abft_build_frames: the steps' candidates are not events but rows of a
+// scratch plane of virtual HighestBefore rows (FcStep::cand = row numbers,
+// FcStep::row0 counts from `bits`)
+struct BuildSteps {
+    const uint32_t *plane;
+    const uint32_t *none;    // LX_NONE per candidate: no candidate is a root slot
+    uint32_t *bits;
+    const BuildArgs *args;   // the own-creator term's tables, on the device
+    const BuildRowsArgs *rows;   // first round: k_build_rows goes between the uploads and the first step
+    bool seq16;              // the candidates' own seqs fit 16 bits
+};
+
 // Many steps in one k_root_fc and one k_root_quorum launch (the MULTI forms;
 // the arena already holds room for every row): enqueued, nothing waits.
-int launch_fc_steps(lx_abft *a, const IndexView &iv, const std::vector<FcStep> &st, uint8_t *q_dev, PassTimer *pt) {
+// own: the steps of lx_abft_build_frames -- nothing of the engine's state or
+// of the last batch's stats is written.
+int launch_fc_steps(lx_abft *a, const IndexView &iv, const std::vector<FcStep> &st, uint8_t *q_dev, PassTimer *pt,
+                    const BuildSteps *own = nullptr) {
     if (st.empty()) return 0;
     hipStream_t s = iv.stream;
     uint64_t ncand = 0, tiles = 0;
@@ -669,14 +690,14 @@ int launch_fc_steps(lx_abft *a, const IndexView &iv, const std::vector<FcStep> &
         Frame &fr = a->frames[x.frame];
         a->up.add(a->d_cand.p + coff, x.cand, x.n_cand * 4ull);
         RootFcArgs &r = fa[j];
-        r.hb = iv.hb;
+        r.hb = own ? own->plane : iv.hb;
         r.la = iv.la;
         r.stride = iv.stride;
         r.cand = a->d_cand.p + coff;
         r.n_cand = x.n_cand;
         r.roots = fr.d_ev.p;
         r.n_roots = x.n_roots;
-        r.roots_fallback = x.cand[0];
+        r.roots_fallback = own ? fr.ev[0] : x.cand[0];
         r.ncols = ncols;
         r.wpad = iv.wpad;
         r.quorum = a->quorum;
@@ -690,15 +711,16 @@ int launch_fc_steps(lx_abft *a, const IndexView &iv, const std::vector<FcStep> &
         r.col_split = col_split;
         r.n_split = n_split;
         r.block0 = blocks;
+        r.own = own ? own->args : nullptr;
         blocks += lx::root_fc_blocks(r);
         QuorumArgs &q = qa[j];
         q.psum = r.psum;
         q.n_split = n_split;
-        q.bits = a->arena.p + x.row0;
+        q.bits = (own ? own->bits : a->arena.p) + x.row0;
         q.words = x.words;
         q.n_roots = x.n_roots;
         q.n_cand = x.n_cand;
-        q.cand = r.cand;
+        q.cand = own ? own->none : r.cand;
         q.root_ev = fr.d_ev.p;
         q.creator = fr.d_creator.p;
         q.dup = fr.d_dup.p;
@@ -711,14 +733,28 @@ int launch_fc_steps(lx_abft *a, const IndexView &iv, const std::vector<FcStep> &
         poff += (uint64_t)n_split * x.n_cand * x.words * 32;
         pairs += (uint64_t)x.n_cand * x.n_roots;
     }
-    a->stats.fc_pairs += pairs;
-    a->stats.fc_pair_cols += pairs * iv.V;
+    if (!own) {
+        a->stats.fc_pairs += pairs;
+        a->stats.fc_pair_cols += pairs * iv.V;
+    }
     a->up.add(a->d_fcargs.p, fa.data(), fa.size() * sizeof(RootFcArgs));
     a->up.add(a->d_qargs.p, qa.data(), qa.size() * sizeof(QuorumArgs));
     if (pt) pt->mark("args");
     ARC(flush_uploads(a, s));
     if (pt) pt->mark("upload");
-    const bool forks = iv.B > iv.V, seq16 = a->fc16 && iv.max_seq <= 0xFFFFu;
+    const bool forks = iv.B > iv.V, seq16 = a->fc16 && iv.max_seq <= 0xFFFFu && (!own || own->seq16);
+    if (own) {
+        if (own->rows) {
+            AHIP(a, lx::launch_build_rows(*own->rows, forks, s));
+            a->bstats.launches++;
+        }
+        AHIP(a, lx::launch_root_fc_own_multi(a->d_fcargs.p, (uint32_t)st.size(), blocks, forks, seq16, s));
+        AHIP(a, lx::launch_root_quorum_multi(a->d_qargs.p, (uint32_t)st.size(), qblocks, s));
+        a->bstats.launches += 2;
+        a->bstats.fc_pairs += pairs;
+        a->bstats.fc16 = !forks && seq16;
+        return 0;
+    }
     const uint32_t k = a->fc_ev_used;
     while (a->fc_ev.size() < 2ull * (k + 1)) {
         hipEvent_t e;
@@ -1755,6 +1791,174 @@ int process_pass(lx_abft *a, uint32_t n, const uint32_t *creator, const uint32_t
     return 0;
 }
 
+// ---------------------------------------------------------------------------- Build without Add
+// lx_abft_build_frames.  A candidate's frame depends on
+// nothing that is not in the planes already: its HighestBefore row is the join
+// of its parents' rows (k_build_rows), and ForklessCause against a frame's
+// roots reads that row and the roots' LowestAfter rows, with the own-creator
+// term corrected for the entries Add would have written (fc_own_term).  The
+// frame loop of calcFrameIdx runs in rounds: every candidate still climbing
+// asks q_f at its current frame, the candidates of one frame are one step of a
+// merged launch, one wait per round.  Nothing of the engine's state is
+// written: the frames' device mirrors are completed (sync_frame), scratch
+// buffers grow, and that is all.
+struct BuildCand {
+    uint32_t pos;      // position in the call
+    uint32_t spf;      // selfParentFrame
+    uint32_t f;        // the loop's current frame
+};
+
+int build_frames(lx_abft *a, uint32_t n, const uint32_t *creator, const uint32_t *seq, const uint64_t *poff,
+                 const uint32_t *par, uint32_t *out_frame, uint8_t *out_is_root, uint32_t *err_index) {
+    IndexView iv;
+    int rc = lx_index_peek(a->ix, &iv);
+    if (rc) return a->ixfail(rc);
+    IndexHostMeta hm;
+    if ((rc = lx_index_host_meta(a->ix, &hm))) return a->ixfail(rc);
+    const uint64_t n_ev = std::min<uint64_t>(iv.n_events, a->ev_frame.size());
+    auto bad = [&](uint32_t i, const char *what) {
+        if (err_index) *err_index = i;
+        return a->fail(LX_ERR_ARG, "candidate %u: %s", i, what);
+    };
+    // ---- input checks (host tables only)
+    std::vector<BuildCand> act;
+    std::vector<uint32_t> tab_br, tab_seq, tab_cr, tab_poff{0}, tab_par, srt;
+    uint32_t cand_max_seq = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        const uint32_t c = creator[i], s = seq[i];
+        if (c >= a->V) return bad(i, "creator out of range");
+        if (s == 0) return bad(i, "seq 0");
+        if (poff[i + 1] < poff[i] || poff[i + 1] - poff[i] > 0xFFFFFFFFull) return bad(i, "parent offsets not monotone");
+        const uint64_t p0 = poff[i], p1 = poff[i + 1];
+        if (p1 > p0 && !par) return bad(i, "null parents");
+        for (uint64_t p = p0; p < p1; p++)
+            if (par[p] >= n_ev) return bad(i, "parent out of range");
+        srt.assign(par + p0, par + p1);
+        std::sort(srt.begin(), srt.end());
+        if (std::adjacent_find(srt.begin(), srt.end()) != srt.end()) return bad(i, "duplicate parent");
+        const bool own_first = p1 > p0 && hm.ev_creator[par[p0]] == c;
+        if (s == 1) {
+            if (own_first) return bad(i, "seq 1 with a self-parent");
+            if (hm.branch_len[c]) return bad(i, "would open a new branch (the creator has events); use lx_abft_build");
+            continue;   // no self-parent: f = 0, roots(0) is empty -> frame 1
+        }
+        if (!own_first || hm.ev_seq[par[p0]] != s - 1) return bad(i, "no self-parent of the same creator at seq - 1");
+        const uint32_t sp = par[p0], br = hm.ev_branch[sp];
+        if (hm.branch_first[br] + hm.branch_len[br] - 1 != s - 1)
+            return bad(i, "would open a new branch (the self-parent is not its branch's last event); use lx_abft_build");
+        if ((uint64_t)tab_par.size() + (p1 - p0) > 0xFFFFFFFFull) return bad(i, "too many parents");
+        const uint32_t spf = a->ev_frame[sp];
+        act.push_back(BuildCand{i, spf, spf});
+        tab_br.push_back(br);
+        tab_seq.push_back(s);
+        tab_cr.push_back(c);
+        tab_par.insert(tab_par.end(), par + p0, par + p1);
+        tab_poff.push_back((uint32_t)tab_par.size());
+        cand_max_seq = std::max(cand_max_seq, s);
+    }
+    for (uint32_t i = 0; i < n; i++) {
+        out_frame[i] = 1;
+        if (out_is_root) out_is_root[i] = 1;
+    }
+    const uint32_t m = (uint32_t)act.size();
+    if (!m) return 0;
+
+    // ---- the virtual rows
+    if ((rc = lx_index_view(a->ix, &iv))) return a->ixfail(rc);   // the pending small-batch run is in the planes
+    if (iv.shard_count > 1 || iv.loading) return a->fail(LX_ERR_STATE, "abft needs an unsharded, loaded index");
+    hipStream_t s = iv.stream;
+    ARC(reserve(a, a->b_plane, (uint64_t)m * iv.stride, 0, s));
+    const uint64_t o_seq = m, o_cr = 2ull * m, o_poff = 3ull * m, o_par = 4ull * m + 1;
+    ARC(reserve(a, a->b_tab, o_par + tab_par.size(), 0, s));
+    a->up.add(a->b_tab.p, tab_br.data(), m * 4ull);
+    a->up.add(a->b_tab.p + o_seq, tab_seq.data(), m * 4ull);
+    a->up.add(a->b_tab.p + o_cr, tab_cr.data(), m * 4ull);
+    a->up.add(a->b_tab.p + o_poff, tab_poff.data(), (m + 1) * 4ull);
+    a->up.add(a->b_tab.p + o_par, tab_par.data(), tab_par.size() * 4ull);
+    if (a->b_none_n < m) {
+        ARC(reserve(a, a->b_none, m, 0, s));
+        const std::vector<uint32_t> none(a->b_none.cap, NONE);
+        a->up.add(a->b_none.p, none.data(), none.size() * 4ull);
+        a->b_none_n = a->b_none.cap;
+    }
+    BuildArgs ba{};
+    ba.br = a->b_tab.p;
+    ba.seq = a->b_tab.p + o_seq;
+    ba.creator = a->b_tab.p + o_cr;
+    ba.par_off = a->b_tab.p + o_poff;
+    ba.par = a->b_tab.p + o_par;
+    ba.ev_seq = iv.ev_seq;
+    ba.cheat_of = iv.cheat_of;
+    ba.cheat_off = iv.cheat_off;
+    ba.cheat_br = iv.cheat_br;
+    ARC(reserve(a, a->b_args, 1, 0, s));
+    a->up.add(a->b_args.p, &ba, sizeof ba);
+    BuildSteps own{};
+    own.args = a->b_args.p;
+    own.plane = a->b_plane.p;
+    own.none = a->b_none.p;
+    own.seq16 = cand_max_seq <= 0xFFFFu;
+    BuildRowsArgs ra{};
+    ra.hb = iv.hb;
+    ra.stride = iv.stride;
+    ra.B = iv.B;
+    ra.plane = a->b_plane.p;
+    ra.n = m;
+    ra.c = ba;
+    ra.branch_first = iv.branch_first;
+    for (const auto &l : *iv.by_creator) ra.n_cheat += l.size() > 1;
+    const uint64_t up0 = a->up.launches;
+    own.rows = &ra;   // the tables, the first round's steps and candidates go up in one k_scatter launch
+
+    // ---- the frame loop, one wait per round
+    std::vector<uint32_t> live(m);
+    for (uint32_t k = 0; k < m; k++) live[k] = k;
+    std::map<uint32_t, std::vector<uint32_t>> by_frame;
+    std::vector<FcStep> st;
+    while (!live.empty()) {
+        by_frame.clear();
+        for (uint32_t k : live) by_frame[act[k].f].push_back(k);
+        st.clear();
+        uint64_t rows = 0, qn = 0;
+        for (auto &kv : by_frame) {
+            const uint32_t f = kv.first;
+            const uint32_t R = f < a->frames.size() ? (uint32_t)a->frames[f].ev.size() : 0;
+            if (!R) continue;   // no roots: no quorum, the loop stops at f
+            const uint32_t words = (R + 31) / 32, nc = (uint32_t)kv.second.size();
+            st.push_back(FcStep{f, kv.second.data(), nc, R, words, rows, qn});
+            rows += (uint64_t)nc * words;
+            qn += nc;
+        }
+        if (st.empty()) {
+            ARC(flush_uploads(a, s));   // nothing asks: leave no upload pending
+            break;
+        }
+        ARC(reserve(a, a->b_bits, rows + 1, 0, s));
+        own.bits = a->b_bits.p;
+        uint8_t *q_dev = nullptr;
+        ARC(q_buffer(a, qn, s, &q_dev));
+        ARC(launch_fc_steps(a, iv, st, q_dev, nullptr, &own));
+        own.rows = nullptr;
+        AHIP(a, hipStreamSynchronize(s));
+        a->bstats.frame_steps += (uint32_t)st.size();
+        a->bstats.rounds++;
+        live.clear();
+        for (const FcStep &x : st)
+            for (uint32_t j = 0; j < x.n_cand; j++) {
+                BuildCand &c = act[x.cand[j]];
+                if (!a->q_pin[x.qoff + j]) continue;
+                c.f++;
+                if (c.f < c.spf + kBuildCap) live.push_back(x.cand[j]);
+            }
+    }
+    a->bstats.launches += (uint32_t)(a->up.launches - up0);
+    for (const BuildCand &c : act) {
+        out_frame[c.pos] = c.f;
+        if (out_is_root) out_is_root[c.pos] = c.f != c.spf;
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1785,6 +1989,11 @@ void lx_abft_destroy(lx_abft *a) {
     a->ea_args.release();
     a->d_fcargs.release();
     a->d_qargs.release();
+    a->b_plane.release();
+    a->b_tab.release();
+    a->b_bits.release();
+    a->b_none.release();
+    a->b_args.release();
     (void)hipDeviceSynchronize();   // queued work may still use pooled buffers
     a->up.release();
     if (a->q_pin) (void)hipHostFree(a->q_pin);
@@ -1932,6 +2141,25 @@ int lx_abft_build(lx_abft *a, uint32_t creator, uint32_t seq, uint32_t np, const
     int rc2 = lx_drop_not_flushed(a->ix);
     if (rc) return rc;
     if (rc2) return a->ixfail(rc2);
+    return 0;
+}
+
+int lx_abft_build_frames(lx_abft *a, uint32_t n, const uint32_t *creator, const uint32_t *seq, const uint64_t *poff,
+                         const uint32_t *par, uint32_t *out_frame, uint8_t *out_is_root, uint32_t *err_index) {
+    if (!a) return LX_ERR_ARG;
+    a->bstats = lx_abft_build_stats{};
+    if (err_index) *err_index = 0;
+    if (!a->booted) return a->fail(LX_ERR_STATE, "not bootstrapped");
+    if (!n) return 0;
+    if (!creator || !seq || !poff || !out_frame) return a->fail(LX_ERR_ARG, "null input");
+    const int rc = build_frames(a, n, creator, seq, poff, par, out_frame, out_is_root, err_index);
+    if (rc == LX_ERR_ARG) a->bstats = lx_abft_build_stats{};
+    return rc;
+}
+
+int lx_abft_build_last_stats(const lx_abft *a, lx_abft_build_stats *out) {
+    if (!a || !out) return LX_ERR_ARG;
+    *out = a->bstats;
     return 0;
 }
 

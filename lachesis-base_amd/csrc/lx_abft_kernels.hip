@@ -63,8 +63,66 @@ __device__ __forceinline__ RootFcArgs fc_step(const RootFcArgs *am, uint32_t n_s
     return a;
 }
 
+// lx_abft_build_frames (OWN): the candidate is not in the index, so column
+// be = its own branch of LA(r) is stale -- Add would have written
+// LA(x)[be] = seq(e) into every ancestor x whose entry was unset.  Once e is
+// added, 0 < LA(r)[be] <= seq(e) holds exactly when r is an ancestor of e (a
+// branch is a chain), so the creator of e counts (once across its branches)
+// iff its own entry is not marked and r is a parent of e or an ancestor of
+// one.  A set stale entry is <= seq(self-parent): whatever the loops above
+// counted for the creator stays right, and only the missing stake is added.
+// Ancestor test: fork-free row[branch(r)] >= seq(r); with forks the exact
+// rule, some parent p with r == p or 0 < LA(r)[branch(p)] <= seq(p).
+template <bool FORKS>
+__device__ __forceinline__ void fc_own_term(const RootFcArgs &a, const BuildArgs &o, const uint32_t (&ev)[4],
+                                            const uint32_t (&rt)[4], uint32_t (&sum)[4][4]) {
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const uint32_t c = ev[i];   // row of the scratch plane = candidate
+        const uint32_t *row = a.hb + (uint64_t)c * a.stride;
+        const uint32_t be = o.br[c], cr = o.creator[c];
+        if (FORKS && (row[be] >> 31)) continue;
+        const uint32_t w = a.wpad[cr];
+        const uint32_t *bl = nullptr;   // the creator's branches (a cheater's: the CSR list)
+        uint32_t nb = 1;
+        if (FORKS) {
+            const int32_t ch = o.cheat_of[cr];
+            if (ch >= 0) {
+                bl = o.cheat_br + o.cheat_off[ch];
+                nb = o.cheat_off[ch + 1] - o.cheat_off[ch];
+            }
+        }
+        const uint32_t p0 = o.par_off[c], p1 = o.par_off[c + 1];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const uint32_t r = rt[k];
+            if (r == LX_NONE) continue;
+            const uint32_t *lr = a.la + (uint64_t)r * a.stride;
+            bool counted = false;
+            for (uint32_t t = 0; t < nb; t++) {
+                const uint32_t j = bl ? bl[t] : be;
+                counted |= (lr[j] - 1u) < hb_prep<FORKS>(row[j]);
+            }
+            if (counted) continue;
+            bool anc = false;
+            if (!FORKS) {
+                anc = row[a.ev_branch[r]] >= o.ev_seq[r];
+            } else {
+                for (uint32_t p = p0; p < p1; p++) {
+                    const uint32_t x = o.par[p];
+                    anc |= x == r || (lr[a.ev_branch[x]] - 1u) < o.ev_seq[x];
+                }
+            }
+            if (anc) sum[i][k] += w;
+        }
+    }
+}
+
 // fc_term of k_fc in staged form: (la - 1) < hb'  <=>  la != 0 && la <= hb
-template <bool FORKS, bool MULTI>
+// OWN: the rows come from the scratch plane of lx_abft_build_frames (a.hb = the
+// plane, a.cand = its rows) and the own-creator term is added (fc_own_term,
+// tables at a.own); the kernels without it compile as before.
+template <bool FORKS, bool MULTI, bool OWN = false>
 __global__ __launch_bounds__(256) void k_root_fc(RootFcArgs a1, const RootFcArgs *am, uint32_t n_steps) {
     uint32_t bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
     const RootFcArgs a = MULTI ? fc_step(am, n_steps, &bx, &by, &bz) : a1;
@@ -167,6 +225,8 @@ __global__ __launch_bounds__(256) void k_root_fc(RootFcArgs a1, const RootFcArgs
         }
     }
 
+    if (OWN && bz == 0) fc_own_term<FORKS>(a, *a.own, ev, rt, sum);
+
     // partial stake sums of this column split; split 0 also carries the
     // cheater fix-ups and the early-false flag (bit 31: total weight < 2^31)
     const uint32_t rp = a.words * 32;
@@ -210,7 +270,7 @@ __device__ __forceinline__ uint32_t udot2(uint32_t a, uint32_t b, uint32_t c) {
     return __builtin_amdgcn_udot2(__builtin_bit_cast(lx_u16x2, a), __builtin_bit_cast(lx_u16x2, b), c, false);
 }
 
-template <bool MULTI>
+template <bool MULTI, bool OWN = false>
 __global__ __launch_bounds__(256) void k_root_fc16(RootFcArgs a1, const RootFcArgs *am, uint32_t n_steps) {
     uint32_t bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
     const RootFcArgs a = MULTI ? fc_step(am, n_steps, &bx, &by, &bz) : a1;
@@ -313,6 +373,20 @@ uint32_t t[4][4];
         __syncthreads();
     }
 
+    if (OWN && bz == 0) {
+        // the own-creator stake goes to the low accumulator whole (the sum of
+        // all stakes is below 2^31)
+        uint32_t ev[4], rt[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const uint32_t ei = e0 + ty * 4 + i;
+            ev[i] = ei < a.n_cand ? a.cand[ei] : a.cand[0];
+            const uint32_t ri = r0 + tx * 4 + i;
+            rt[i] = ri < a.n_roots ? a.roots[ri] : LX_NONE;
+        }
+        fc_own_term<false>(a, *a.own, ev, rt, lo);
+    }
+
     // partial stake sums of this column split (no cheaters, no early-false flag)
     const uint32_t rp = a.words * 32;
 #pragma unroll
@@ -359,6 +433,19 @@ hipError_t launch_root_fc_multi(const RootFcArgs *am, uint32_t n_steps, uint32_t
     if (!forks && seq16) hipLaunchKernelGGL(k_root_fc16<true>, dim3(blocks), dim3(256), 0, s, RootFcArgs{}, am, n_steps);
     else if (forks) hipLaunchKernelGGL((k_root_fc<true, true>), dim3(blocks), dim3(256), 0, s, RootFcArgs{}, am, n_steps);
     else hipLaunchKernelGGL((k_root_fc<false, true>), dim3(blocks), dim3(256), 0, s, RootFcArgs{}, am, n_steps);
+    return hipGetLastError();
+}
+
+// the frame steps of lx_abft_build_frames: rows of the scratch plane, own-creator term
+hipError_t launch_root_fc_own_multi(const RootFcArgs *am, uint32_t n_steps, uint32_t blocks, bool forks, bool seq16,
+                                    hipStream_t s) {
+    if (!n_steps || !blocks) return hipSuccess;
+    if (!forks && seq16)
+        hipLaunchKernelGGL((k_root_fc16<true, true>), dim3(blocks), dim3(256), 0, s, RootFcArgs{}, am, n_steps);
+    else if (forks)
+        hipLaunchKernelGGL((k_root_fc<true, true, true>), dim3(blocks), dim3(256), 0, s, RootFcArgs{}, am, n_steps);
+    else
+        hipLaunchKernelGGL((k_root_fc<false, true, true>), dim3(blocks), dim3(256), 0, s, RootFcArgs{}, am, n_steps);
     return hipGetLastError();
 }
 

@@ -3424,3 +3424,20 @@ int lx_index_peek(lx_index *h, IndexView *o) {
     o->loading = h->loading;
     return 0;
 }
+
+// the host mirror of the per-event metadata (hm_sync: waits for the stream only
+// after batches the device assigned); see lx_internal.h
+int lx_index_host_meta(lx_index *h, IndexHostMeta *o) {
+    if (!h || !o) return LX_ERR_ARG;
+    WHOLE_INDEX(h);
+    if (!h->have_epoch) return h->fail(LX_ERR_STATE, "index has no epoch (lx_reset first)");
+    HIPCHK(h, set_dev(h->device));
+    const int rc = hm_sync(h);
+    if (rc) return rc;
+    o->ev_creator = h->hm_creator.data();
+    o->ev_seq = h->hm_seq.data();
+    o->ev_branch = h->hm_branch.data();
+    o->branch_len = h->hm_blen.data();
+    o->branch_first = h->h_branch_first.data();
+    return 0;
+}

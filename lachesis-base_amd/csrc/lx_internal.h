@@ -635,6 +635,20 @@ struct AncArgs {
 };
 
 // ---- batched abft caller (lx_abft_kernels.hip, lx_abft.cpp)
+// lx_abft_build_frames: n candidate events that are not added.  Candidate c is
+// row c of a scratch plane (k_build_rows, lx_abft_build.hip); the OWN forms of
+// the root-FC kernels read the per-candidate tables for the own-creator term.
+struct BuildArgs {
+    const uint32_t *br;          // [n] the branch the candidate extends
+    const uint32_t *seq;         // [n]
+    const uint32_t *creator;     // [n]
+    const uint32_t *par_off;     // [n + 1] into par
+    const uint32_t *par;         // parents (dense events), self-parent first
+    const uint32_t *ev_seq;
+    const int32_t *cheat_of;     // creator -> cheater index (-1: one branch); CSR as IndexView
+    const uint32_t *cheat_off;
+    const uint32_t *cheat_br;
+};
 struct RootFcArgs {
     const uint32_t *hb;
     const uint32_t *la;
@@ -657,6 +671,7 @@ struct RootFcArgs {
     uint32_t col_split;          // columns per split (multiple of 32)
     uint32_t n_split;            // column splits (grid z)
     uint32_t block0;             // merged launch: this step's first workgroup
+    const BuildArgs *own;        // lx_abft_build_frames (the OWN kernels): the candidates' tables, on the device
 };
 
 constexpr uint32_t kMaxFrameRoots = 16384;   // k_root_quorum keeps a candidate's bit row in LDS
@@ -675,6 +690,17 @@ struct QuorumArgs {
     uint32_t quorum;
     uint8_t *q;                  // out
     uint32_t block0;             // merged launch: this step's first workgroup
+};
+
+struct BuildRowsArgs {
+    const uint32_t *hb;
+    uint64_t stride;
+    uint32_t B;                  // branches now
+    uint32_t *plane;             // out: [n][stride]
+    uint32_t n;
+    BuildArgs c;
+    const uint32_t *branch_first;
+    uint32_t n_cheat;
 };
 
 constexpr uint32_t kVoteVoted = 0x80000000u, kVoteYes = 0x40000000u, kVoteDecided = 0x20000000u,
@@ -879,6 +905,9 @@ hipError_t launch_root_fc(const RootFcArgs &a, bool forks, bool seq16, hipStream
 uint32_t root_fc_blocks(const RootFcArgs &a);
 hipError_t launch_root_fc_multi(const RootFcArgs *am, uint32_t n_steps, uint32_t blocks, bool forks, bool seq16,
                                 hipStream_t s);
+hipError_t launch_root_fc_own_multi(const RootFcArgs *am, uint32_t n_steps, uint32_t blocks, bool forks, bool seq16,
+                                    hipStream_t s);
+hipError_t launch_build_rows(const BuildRowsArgs &a, bool forks, hipStream_t s);   // lx_abft_build.hip
 hipError_t launch_root_quorum_multi(const QuorumArgs *am, uint32_t n_steps, uint32_t blocks, hipStream_t s);
 hipError_t launch_root_quorum(const QuorumArgs &a, hipStream_t s);
 hipError_t launch_fc_tile_out(const uint32_t *psum, uint32_t n_split, uint32_t n_cand, uint32_t rp, uint32_t n_roots,
@@ -929,6 +958,15 @@ int lx_index_view(lx_index *h, IndexView *out);
 // it, the device tables may not hold it yet.  For callers that enqueue nothing
 // that reads those events' rows
 int lx_index_peek(lx_index *h, IndexView *out);
+// Host copies of the immutable per-event fields (every event of the epoch, the
+// pending small-batch run included) and of the branch tables, for callers that
+// check input before any device work.  Valid until the next call that adds or
+// drops events.
+struct IndexHostMeta {
+    const uint32_t *ev_creator, *ev_seq, *ev_branch;   // [n_events]
+    const uint32_t *branch_len, *branch_first;         // [B]: events on the branch, its first seq
+};
+int lx_index_host_meta(lx_index *h, IndexHostMeta *out);
 // events that kept their dense index through every rollback after generation
 // `gen` (a roll_gen seen earlier): the smallest flushed count any of them left
 uint64_t lx_index_kept_since(const lx_index *h, uint64_t gen);

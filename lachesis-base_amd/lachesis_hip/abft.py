@@ -12,6 +12,9 @@ abft/common_test.go drives FakeLachesis:
 * ``build(e)`` / ``process(e)``            -- Build / Process
   (abft/indexed_lachesis.go:53-82); ``process_batch(events)`` processes many
   events in one call with the same results
+* ``build_frames(events)``                 -- Build for candidate events that are
+  not added (lx_abft_build_frames): sets ``e.frame``, returns the is-root
+  flags; no Add, no rollback
 * ``reset(epoch, validators)``             -- Orderer.Reset (abft/bootstrap.go:54-65)
 * ``state()`` / ``restore(state, index_db, get_event, begin_block)`` -- the
   abft state a caller persists, and Bootstrap over it after a restart
@@ -84,6 +87,35 @@ class AbftStats(ctypes.Structure):
                 ("vote_launches", ctypes.c_uint32), ("blocks", ctypes.c_uint32), ("fc_pairs", ctypes.c_uint64),
                 ("fc_pair_cols", ctypes.c_uint64), ("ms_root_fc_gpu", ctypes.c_float),
                 ("fc_lane_ops", ctypes.c_uint64), ("elections_ahead", ctypes.c_uint32)]
+
+
+class BuildStats(ctypes.Structure):
+    """lx_abft_build_stats."""
+    _fields_ = [("launches", ctypes.c_uint32), ("frame_steps", ctypes.c_uint32), ("rounds", ctypes.c_uint32),
+                ("fc16", ctypes.c_uint32), ("fc_pairs", ctypes.c_uint64)]
+
+
+def build_frames_arrays(L, h, creator, seq, poff, par, chk=None):
+    """lx_abft_build_frames on dense arrays: (frames, is_root).  Without
+    ``chk`` returns (rc, err_index, frames, is_root) instead of raising."""
+    creator = np.ascontiguousarray(creator, dtype=np.uint32)
+    seq = np.ascontiguousarray(seq, dtype=np.uint32)
+    poff = np.ascontiguousarray(poff, dtype=np.uint64)
+    par = np.ascontiguousarray(par if len(par) else [0], dtype=np.uint32)
+    n = len(creator)
+    frames = np.zeros(max(n, 1), dtype=np.uint32)
+    roots = np.zeros(max(n, 1), dtype=np.uint8)
+    err = ctypes.c_uint32()
+    rc = L.lx_abft_build_frames(h, n, _p(creator, u32p), _p(seq, u32p), _p(poff, u64p), _p(par, u32p),
+                                _p(frames, u32p), roots.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
+                                ctypes.byref(err))
+    if chk is None:
+        return rc, err.value, frames[:n], roots[:n]
+    if rc != 0:
+        ex = LxError(rc, L.lx_abft_last_error(h).decode())
+        ex.err_index = err.value
+        raise ex
+    return frames[:n], roots[:n]
 
 
 class AbftState(ctypes.Structure):
@@ -293,6 +325,30 @@ class IndexedLachesis:
         self._chk(self.L.lx_abft_build(self.h, int(creator[0]), int(seq[0]), n, _p(flat, u32p), ctypes.byref(out)))
         e.frame = out.value
 
+    def build_frames(self, events):
+        """Build for candidate events that are not added (lx_abft_build_frames):
+        sets ``e.frame`` on each -- what :meth:`build` would set -- and returns
+        the is-root flags (frame != selfParentFrame).  Each candidate is judged
+        alone; parents are existing events.  Nothing is added or rolled back.
+        A refused candidate raises LxError with ``err_index`` = its position."""
+        creator = np.array([self.validators.idxs[e.creator] for e in events], dtype=np.uint32)
+        seq = np.array([e.seq for e in events], dtype=np.uint32)
+        off = np.zeros(len(events) + 1, dtype=np.uint64)
+        flat = []
+        for k, e in enumerate(events):
+            flat.extend(self.pos[p] for p in e.parents)
+            off[k + 1] = len(flat)
+        frames, roots = build_frames_arrays(self.L, self.h, creator, seq, off, flat, self._chk)
+        for e, f in zip(events, frames):
+            e.frame = int(f)
+        return [bool(r) for r in roots]
+
+    def build_stats(self):
+        """lx_abft_build_last_stats: GPU work of the last :meth:`build_frames`."""
+        st = BuildStats()
+        self._chk(self.L.lx_abft_build_last_stats(self.h, ctypes.byref(st)))
+        return {f: getattr(st, f) for f, _ in BuildStats._fields_}
+
     def process(self, e):
         """Process (indexed_lachesis.go:65-82): None or the error."""
         consumed, err = self.process_batch([e])
@@ -494,6 +550,24 @@ class DenseLachesis:
         for k in range(n):
             self.blocks.append((ep, fr[k], at[k], tuple(ch[i] for i in range(co[k], co[k + 1])),
                                 tuple(cf[i] for i in range(fo[k], fo[k + 1]))))
+
+    def build(self, creator, seq, parents):
+        """lx_abft_build: the frame of one event (added, evaluated, dropped)."""
+        p = np.ascontiguousarray(parents if len(parents) else [0], dtype=np.uint32)
+        out = ctypes.c_uint32()
+        self._chk(self.L.lx_abft_build(self.h, int(creator), int(seq), len(parents), _p(p, u32p), ctypes.byref(out)))
+        return out.value
+
+    def build_frames(self, creator, seq, poff, par):
+        """lx_abft_build_frames: (rc, err_index, frames, is_root) of candidate
+        events that are not added."""
+        return build_frames_arrays(self.L, self.h, creator, seq, poff, par)
+
+    def build_stats(self):
+        """lx_abft_build_last_stats."""
+        st = BuildStats()
+        self._chk(self.L.lx_abft_build_last_stats(self.h, ctypes.byref(st)))
+        return {f: getattr(st, f) for f, _ in BuildStats._fields_}
 
     def epoch(self):
         return self.L.lx_abft_epoch(self.h)

@@ -123,6 +123,9 @@ SIGNATURES = [
     ("lx_abft_reset", ctypes.c_int, [vp, ctypes.c_uint32, ctypes.c_uint32, u32p]),
     ("lx_abft_process_batch", ctypes.c_int, [vp, ctypes.c_uint32, u32p, u32p, u64p, u32p, u32p, u32p, u32p]),
     ("lx_abft_build", ctypes.c_int, [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, u32p, u32p]),
+    ("lx_abft_build_frames", ctypes.c_int, [vp, ctypes.c_uint32, u32p, u32p, u64p, u32p, u32p,
+                                            ctypes.POINTER(ctypes.c_uint8), u32p]),
+    ("lx_abft_build_last_stats", ctypes.c_int, [vp, vp]),
     ("lx_abft_epoch", ctypes.c_uint32, [vp]),
     ("lx_abft_last_decided_frame", ctypes.c_uint32, [vp]),
     ("lx_abft_frame_roots", ctypes.c_int, [vp, ctypes.c_uint32, u32p, ctypes.c_uint32, u32p]),
