@@ -53,8 +53,33 @@
  * from inside the begin_block, apply_event and end_block callbacks of
  * lx_abft_process_batch.
  *
+ * Fork evidence.  The cheaters of a block (applyAtropos, abft/lachesis.go:
+ * 56-74) and the fork markers of a merged HighestBefore row only name a
+ * creator.  lx_anc_fork_pairs / lx_anc_cheaters name the two events that prove
+ * it, by the reference's own definition of a fork (the naive detection of
+ * testForksDetected, vecfc/forkless_cause_test.go:490-518): head observes a
+ * fork of creator c  <=>  two different events of c with the same seq are head
+ * or ancestors of head.  With S(head, c) = the events of c that are head or
+ * ancestors of it, the answer is canonical:
+ *   - seq* = the lowest seq two events of S share;
+ *   - x < y = the two lowest dense indices among the events of S with seq*
+ *     (three and more events in one slot do occur);
+ *   - (LX_ANC_NONE, LX_ANC_NONE, 0) where no two events of S share a seq.
+ * No parent list is read: a branch is a chain of consecutive seqs, so head's
+ * view of a branch is an interval of seqs whose end a binary search over the
+ * branch's events finds, and seq* is the lowest seq two intervals of c's
+ * branches share.  The search asks the LowestAfter rule above, not
+ * HighestBefore: once head has detected the fork EVERY branch entry of c in
+ * its row is a marker (Seq 0) and says nothing of how far head sees.  The
+ * marker only serves as the quick "none": the reference marks a creator
+ * exactly where S holds such a pair.
+ * The calls keep no state but the list of the last lx_anc_cheaters (empty
+ * after a new epoch or a rollback that dropped events, as
+ * lx_anc_last_confirmed), and neither read nor write labels.
+ *
  * Out of scope: column-sharded and row-segment handles (LX_ERR_STATE), the
- * reference's DFS order, the general walk filter of DfsSubgraph.
+ * reference's DFS order, the general walk filter of DfsSubgraph, evidence
+ * other than the canonical lowest pair.
  */
 #ifndef LACHESIS_ANCESTRY_H
 #define LACHESIS_ANCESTRY_H
@@ -100,6 +125,30 @@ int lx_anc_set_labels(lx_anc *a, uint64_t first, uint64_t n, const uint32_t *lab
 /* The lowest dense index without a label (= lx_num_events when all have one):
  * no event below it is looked at by lx_anc_confirm. */
 int lx_anc_low_water(lx_anc *a, uint64_t *ev);
+
+/* "no event" in the answers of the fork-evidence calls */
+#define LX_ANC_NONE 0xFFFFFFFFu
+
+/* Pairwise: out_x[i] < out_y[i] = the canonical pair for (head[i], creator[i])
+ * (creator = validator idx), out_seq[i] (optional, may be NULL) their seq;
+ * LX_ANC_NONE, LX_ANC_NONE, 0 where head[i] observes no fork of creator[i].
+ * LX_ERR_ARG for a head that is no indexed event, a creator >= the number of
+ * validators, and an index in which one creator has more than 1024 branches.
+ * A fork-free epoch answers without a launch. */
+int lx_anc_fork_pairs(lx_anc *a, uint64_t n, const uint32_t *head, const uint32_t *creator,
+                      uint32_t *out_x, uint32_t *out_y, uint32_t *out_seq);
+
+/* Every cheater each head observes (= the fork-detected entries of its merged
+ * HighestBefore, the cheaters of applyAtropos when head is an Atropos) with
+ * the pair: n_found[k] of them for head k.  The list is read with
+ * lx_anc_last_cheaters: grouped by head in call order (duplicates repeat),
+ * ascending creator idx inside a group. */
+int lx_anc_cheaters(lx_anc *a, uint32_t n_heads, const uint32_t *head, uint32_t *n_found);
+/* *n = the entries of the last lx_anc_cheaters; the first min(cap, *n) are
+ * written (with cap > 0, out_creator, out_x and out_y are required, out_seq
+ * may be NULL). */
+int lx_anc_last_cheaters(lx_anc *a, uint32_t *out_creator, uint32_t *out_x, uint32_t *out_y,
+                         uint32_t *out_seq, uint64_t cap, uint64_t *n);
 
 #ifdef __cplusplus
 }

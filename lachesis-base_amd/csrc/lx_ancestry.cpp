@@ -6,7 +6,8 @@
 // table is keyed by dense index, so it follows the index's rollbacks as the
 // MedianTime handle does (lx_mediantime.cpp): IndexView::epoch_gen / roll_gen
 // say when indices were given to other events, lx_index_kept_since how many
-// kept theirs.
+// kept theirs.  The fork-evidence calls keep only the list of the last
+// lx_anc_cheaters, which the same generations empty.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -23,6 +24,7 @@ namespace {
 constexpr uint64_t kAncPairChunk = 1ull << 22;   // pairs per launch
 constexpr uint32_t kAncMaxB = kAncLdsBytes / 4;  // one row must fit the LDS budget
 constexpr uint32_t kAncMaxPerWg = 4096;          // events per confirm workgroup, at most
+constexpr uint64_t kAncForkChunk = 1ull << 20;   // (head, cheater) queries of one lx_anc_cheaters launch
 }  // namespace
 
 struct lx_anc {
@@ -42,6 +44,10 @@ struct lx_anc {
     lxi::DevBuf<uint32_t> out_ev;
     lxi::DevBuf<uint32_t> res;              // [n_heads] n_new, then the low-water mark
     lxi::PinBuf<uint32_t> h_res;
+    // fork evidence: the answers of a chunk of queries, and the list of the last lx_anc_cheaters
+    uint64_t last_ch = 0;
+    lxi::DevBuf<uint32_t> d_fx, d_fy, d_fs;
+    lxi::DevBuf<uint32_t> ch_creator, ch_x, ch_y, ch_seq;
 
     int fail(int code, const char *fmt, ...) {
         char buf[512];
@@ -82,13 +88,13 @@ int follow(lx_anc *m, IndexView *iv, bool flush) {
     }
     if (iv->shard_count > 1) return m->fail(LX_ERR_STATE, "ancestry needs an unsharded index");
     if (iv->epoch_gen != m->epoch_gen) {
-        m->n_lab = m->low = m->last_n = 0;
+        m->n_lab = m->low = m->last_n = m->last_ch = 0;
         m->epoch_gen = iv->epoch_gen;
     } else if (iv->roll_gen != m->roll_gen) {
         const uint64_t kept = lx_index_kept_since(m->ix, m->roll_gen);
         m->n_lab = std::min(m->n_lab, kept);
         m->low = std::min(m->low, kept);
-        m->last_n = 0;
+        m->last_n = m->last_ch = 0;
     }
     m->roll_gen = iv->roll_gen;
     int cur = -1;   // (hipSetDevice costs microseconds: only when the device is not current)
@@ -104,6 +110,30 @@ int hold(lx_anc *m, uint64_t need, hipStream_t st) {
     else
         AHIP(m, hipMemsetAsync(m->labels + m->n_lab, 0, (need - m->n_lab) * 4, st));
     m->n_lab = need;
+    return 0;
+}
+
+// the index's tables of a fork-evidence launch; LX_ERR_ARG where a creator has
+// more branches than a wave keeps intervals
+int fork_args(lx_anc *m, const IndexView &iv, AncForkArgs *a) {
+    for (const auto &l : *iv.by_creator)
+        if (l.size() > kAncForkMaxBr)
+            return m->fail(LX_ERR_ARG, "fork evidence supports up to %u branches of one creator", kAncForkMaxBr);
+    *a = AncForkArgs{};
+    a->hb = iv.hb;
+    a->la = iv.la;
+    a->stride = iv.stride;
+    a->ev_branch = iv.ev_branch;
+    a->ev_seq = iv.ev_seq;
+    a->brow = iv.brow;
+    a->branch_first = iv.branch_first;
+    a->branch_len = iv.branch_len;
+    a->s_cap = iv.s_cap;
+    a->cheat_of = iv.cheat_of;
+    a->cheat_off = iv.cheat_off;
+    a->cheat_br = iv.cheat_br;
+    a->cheat_creator = iv.cheat_creator;
+    a->n_cheat = iv.n_cheat;
     return 0;
 }
 
@@ -261,6 +291,140 @@ int lx_anc_last_confirmed(lx_anc *m, uint32_t *out_ev, uint64_t cap, uint64_t *n
     const uint64_t c = std::min(cap, m->last_n);
     if (c) {
         AHIP(m, hipMemcpyAsync(out_ev, m->out_ev, c * 4, hipMemcpyDeviceToHost, iv.stream));
+        AHIP(m, hipStreamSynchronize(iv.stream));
+    }
+    return 0;
+}
+
+int lx_anc_fork_pairs(lx_anc *m, uint64_t n, const uint32_t *head, const uint32_t *creator, uint32_t *out_x,
+                      uint32_t *out_y, uint32_t *out_seq) {
+    if (!m) return LX_ERR_ARG;
+    if (n && (!head || !creator || !out_x || !out_y)) return m->fail(LX_ERR_ARG, "null argument");
+    if (!n) return 0;
+    IndexView iv;
+    ARC(follow(m, &iv, true));
+    if (iv.loading) return m->fail(LX_ERR_STATE, "index is loading (lx_load_finish first)");
+    for (uint64_t i = 0; i < n; i++) {
+        if (head[i] >= iv.n_events) return m->fail(LX_ERR_ARG, "unknown event %u (head)", head[i]);
+        if (creator[i] >= iv.V) return m->fail(LX_ERR_ARG, "unknown creator %u: %u validators", creator[i], iv.V);
+    }
+    if (iv.B == iv.V || !iv.n_cheat) {   // no forks this epoch
+        memset(out_x, 0xFF, n * 4);
+        memset(out_y, 0xFF, n * 4);
+        if (out_seq) memset(out_seq, 0, n * 4);
+        return 0;
+    }
+    AncForkArgs a;
+    ARC(fork_args(m, iv, &a));
+    const uint64_t chunk = std::min(n, kAncPairChunk);
+    // (every launch that read the old buffers has been waited for below)
+    AHIP(m, m->d_head.grow(chunk));
+    AHIP(m, m->d_x.grow(chunk));
+    AHIP(m, m->d_fx.grow(chunk));
+    AHIP(m, m->d_fy.grow(chunk));
+    AHIP(m, m->d_fs.grow(chunk));
+    a.head = m->d_head;
+    a.creator = m->d_x;
+    a.x = m->d_fx;
+    a.y = m->d_fy;
+    a.seq = m->d_fs;
+    for (uint64_t lo = 0; lo < n; lo += chunk) {
+        a.n = std::min(chunk, n - lo);
+        AHIP(m, hipMemcpyAsync(m->d_head, head + lo, a.n * 4, hipMemcpyHostToDevice, iv.stream));
+        AHIP(m, hipMemcpyAsync(m->d_x, creator + lo, a.n * 4, hipMemcpyHostToDevice, iv.stream));
+        AHIP(m, lx::launch_anc_fork(a, iv.stream));
+        AHIP(m, hipMemcpyAsync(out_x + lo, m->d_fx, a.n * 4, hipMemcpyDeviceToHost, iv.stream));
+        AHIP(m, hipMemcpyAsync(out_y + lo, m->d_fy, a.n * 4, hipMemcpyDeviceToHost, iv.stream));
+        if (out_seq) AHIP(m, hipMemcpyAsync(out_seq + lo, m->d_fs, a.n * 4, hipMemcpyDeviceToHost, iv.stream));
+        AHIP(m, hipStreamSynchronize(iv.stream));
+    }
+    return 0;
+}
+
+int lx_anc_cheaters(lx_anc *m, uint32_t n_heads, const uint32_t *head, uint32_t *n_found) {
+    if (!m) return LX_ERR_ARG;
+    if (n_heads && (!head || !n_found)) return m->fail(LX_ERR_ARG, "null argument");
+    IndexView iv;
+    ARC(follow(m, &iv, true));
+    if (iv.loading) return m->fail(LX_ERR_STATE, "index is loading (lx_load_finish first)");
+    for (uint32_t k = 0; k < n_heads; k++)
+        if (head[k] >= iv.n_events) return m->fail(LX_ERR_ARG, "unknown event %u (head %u)", head[k], k);
+    AncForkArgs a{};
+    const bool forks = iv.B != iv.V && iv.n_cheat;
+    if (forks) ARC(fork_args(m, iv, &a));
+    m->last_ch = 0;
+    if (!n_heads) return 0;
+    memset(n_found, 0, n_heads * 4ull);
+    if (!forks) return 0;
+    // launches of whole heads, at most kAncForkChunk queries each (one head at least)
+    const uint32_t H = (uint32_t)std::min<uint64_t>(n_heads, std::max<uint64_t>(1, kAncForkChunk / iv.n_cheat));
+    const uint64_t nq = (uint64_t)H * iv.n_cheat;
+    if (nq + 1 > 0x7FFFFFFFull) return m->fail(LX_ERR_ARG, "too many cheaters for one launch");
+    size_t tmp_bytes = 0;
+    AHIP(m, lx::anc_scan_bytes((uint32_t)(nq + 1), &tmp_bytes));
+    // (every launch that read the old buffers was waited for by the call that made it)
+    AHIP(m, m->d_head.grow(H));
+    AHIP(m, m->d_fx.grow(nq));
+    AHIP(m, m->d_fy.grow(nq));
+    AHIP(m, m->d_fs.grow(nq));
+    AHIP(m, m->cnt.grow(nq + 1));
+    AHIP(m, m->off.grow(nq + 1));
+    AHIP(m, m->tmp.grow(std::max<size_t>(tmp_bytes, 1)));
+    AHIP(m, m->res.grow(H));
+    a.head = m->d_head;
+    a.creator = nullptr;
+    a.x = m->d_fx;
+    a.y = m->d_fy;
+    a.seq = m->d_fs;
+    AncForkListArgs l{};
+    l.x = a.x;
+    l.y = a.y;
+    l.seq = a.seq;
+    l.cheat_creator = iv.cheat_creator;
+    l.n_cheat = iv.n_cheat;
+    l.flag = m->cnt;
+    l.off = m->off;
+    l.n_found = m->res;
+    uint64_t total = 0;
+    for (uint32_t k0 = 0; k0 < n_heads; k0 += H) {
+        l.n_heads = std::min(H, n_heads - k0);
+        a.n = (uint64_t)l.n_heads * iv.n_cheat;
+        // the list holds what the earlier launches found and has room for every query of this one
+        const uint64_t need = total + a.n;
+        if (need > m->ch_x.cap() || !m->ch_x.get()) {
+            const uint64_t cap = std::max<uint64_t>({need, 2 * m->ch_x.cap(), 1024});
+            for (auto *b : {&m->ch_creator, &m->ch_x, &m->ch_y, &m->ch_seq})
+                AHIP(m, b->regrow(cap, total, lxi::Fill::none, iv.stream));
+        }
+        l.base = total;
+        l.out_creator = m->ch_creator;
+        l.out_x = m->ch_x;
+        l.out_y = m->ch_y;
+        l.out_seq = m->ch_seq;
+        AHIP(m, hipMemcpyAsync(m->d_head, head + k0, l.n_heads * 4ull, hipMemcpyHostToDevice, iv.stream));
+        AHIP(m, lx::launch_anc_fork(a, iv.stream));
+        AHIP(m, lx::launch_anc_fork_list(l, m->tmp, tmp_bytes, iv.stream));
+        AHIP(m, hipMemcpyAsync(n_found + k0, m->res, l.n_heads * 4ull, hipMemcpyDeviceToHost, iv.stream));
+        AHIP(m, hipStreamSynchronize(iv.stream));
+        for (uint32_t k = 0; k < l.n_heads; k++) total += n_found[k0 + k];
+    }
+    m->last_ch = total;
+    return 0;
+}
+
+int lx_anc_last_cheaters(lx_anc *m, uint32_t *out_creator, uint32_t *out_x, uint32_t *out_y, uint32_t *out_seq,
+                         uint64_t cap, uint64_t *n) {
+    if (!m) return LX_ERR_ARG;
+    if (!n || (cap && (!out_creator || !out_x || !out_y))) return m->fail(LX_ERR_ARG, "null argument");
+    IndexView iv;
+    ARC(follow(m, &iv, false));
+    *n = m->last_ch;
+    const uint64_t c = std::min(cap, m->last_ch);
+    if (c) {
+        AHIP(m, hipMemcpyAsync(out_creator, m->ch_creator, c * 4, hipMemcpyDeviceToHost, iv.stream));
+        AHIP(m, hipMemcpyAsync(out_x, m->ch_x, c * 4, hipMemcpyDeviceToHost, iv.stream));
+        AHIP(m, hipMemcpyAsync(out_y, m->ch_y, c * 4, hipMemcpyDeviceToHost, iv.stream));
+        if (out_seq) AHIP(m, hipMemcpyAsync(out_seq, m->ch_seq, c * 4, hipMemcpyDeviceToHost, iv.stream));
         AHIP(m, hipStreamSynchronize(iv.stream));
     }
     return 0;

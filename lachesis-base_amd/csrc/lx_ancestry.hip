@@ -22,12 +22,15 @@
 //    workgroup) group in the ordered output)
 //   k_anc_scatter : writes the labels and the events, a wave-ballot prefix
 //                   inside the workgroup keeps a group in ascending order.
+//   k_anc_fork    : fork evidence, one wave per (head, creator) query: the
+//                   pair of events behind a cheater flag (see there).
 //   No kernel waits for another workgroup.
 // Integer gathers; bound by the launches at the sizes of one epoch.
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 
+#include "../../include/lachesis_ancestry.h"
 #include "lx_internal.h"
 
 namespace lx {
@@ -193,7 +196,142 @@ __global__ __launch_bounds__(kAncThreads) void k_anc_low(const uint32_t *labels,
     if (threadIdx.x % 64 == 0 && mn != LX_NONE) atomicMin(low, mn);
 }
 
+// ---- fork evidence: the two events behind a cheater flag
+//
+// A branch is a chain of consecutive seqs and "head observes its k-th event"
+// is monotone in k, so head's view of branch b is an interval of seqs
+// [first_b, hi_b] (or nothing), hi_b found by a binary search over brow[b] with
+// the LowestAfter rule (the HighestBefore entries of a detected cheater are
+// all marks and say nothing).  The lowest seq two intervals share is a first
+// seq: seq* = min { first_j : some i != j has first_i <= first_j <= hi_i }
+// (below the start of both intervals that cover it a shared seq would have a
+// shared predecessor).  The pair: the two lowest events brow[b][seq* - first_b]
+// over the intervals that hold seq*.
+//
+// One wave per query; a lane takes the creator's branches lane, lane + 64, ..
+// of the CSR, the lanes' searches run in lockstep.  The intervals stay in LDS
+// (kAncForkMaxBr per wave, checked by the host).
+__global__ __launch_bounds__(kAncThreads) void k_anc_fork(AncForkArgs a) {
+    __shared__ uint32_t sFirst[kAncForkWaves][kAncForkMaxBr], sHi[kAncForkWaves][kAncForkMaxBr];
+    const uint32_t lane = threadIdx.x % 64, wave = threadIdx.x / 64;
+    const uint64_t q = (uint64_t)blockIdx.x * kAncForkWaves + wave;
+    uint32_t h = 0, c = 0;
+    int32_t k = -1;
+    if (q < a.n) {
+        if (a.creator) {
+            h = a.head[q];
+            c = a.creator[q];
+        } else {
+            h = a.head[q / a.n_cheat];
+            c = a.cheat_creator[q % a.n_cheat];
+        }
+        k = a.cheat_of[c];
+        // marks are per creator: head has not detected the fork where its entry
+        // of the creator's original branch (column c) is no mark
+        if (k >= 0 && !(a.hb[(uint64_t)h * a.stride + c] & LX_MARK)) k = -1;
+    }
+    uint32_t rx = LX_ANC_NONE, ry = LX_ANC_NONE, rs = 0;
+    uint32_t o0 = 0, nb = 0, seen = 0;   // seen: branches head observes, of this lane
+    uint32_t *first = sFirst[wave], *hi = sHi[wave];
+    if (k >= 0) {   // (the same in every lane of the wave)
+        o0 = a.cheat_off[k];
+        nb = a.cheat_off[k + 1] - o0;
+        nb = nb < kAncForkMaxBr ? nb : kAncForkMaxBr;   // (the host refused more)
+        const uint32_t hbr = a.ev_branch[h], hs = a.ev_seq[h];
+        for (uint32_t j = lane; j < nb; j += 64) {
+            const uint32_t b = a.cheat_br[o0 + j];
+            const uint32_t *row = a.brow + (uint64_t)b * a.s_cap;
+            uint32_t lo = 0, up = a.branch_len[b];
+            up = up < a.s_cap ? up : a.s_cap;
+            while (lo < up) {   // events [0, lo) are observed, [up, len) are not
+                const uint32_t mid = (lo + up) / 2, x = row[mid];
+                if (x <= h && anc_marked_observes(a.la, a.stride, x, hbr, hs)) lo = mid + 1;
+                else up = mid;
+            }
+            const uint32_t f = a.branch_first[b];
+            first[j] = lo ? f : LX_ANC_NONE;
+            hi[j] = lo ? f + lo - 1 : 0;
+            seen += lo != 0;
+        }
+    }
+    __syncthreads();   // a wave reads the intervals its other lanes wrote
+    if (k >= 0) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) seen += __shfl_xor(seen, off, 64);
+        if (seen >= 2) {
+            uint32_t best = LX_ANC_NONE;
+            for (uint32_t j = lane; j < nb; j += 64) {
+                const uint32_t f = first[j];
+                if (f == LX_ANC_NONE || f >= best) continue;
+                for (uint32_t i = 0; i < nb; i++)
+                    if (i != j && first[i] <= f && f <= hi[i]) {
+                        best = f;
+                        break;
+                    }
+            }
+            best = wave_min_u32(best);
+            if (best != LX_ANC_NONE) {
+                uint32_t m1 = LX_ANC_NONE, m2 = LX_ANC_NONE;   // the two lowest events of this lane
+                for (uint32_t j = lane; j < nb; j += 64) {
+                    if (first[j] > best || best > hi[j]) continue;
+                    const uint32_t b = a.cheat_br[o0 + j];
+                    const uint32_t e = a.brow[(uint64_t)b * a.s_cap + (best - first[j])];
+                    if (e < m1) m2 = m1, m1 = e;
+                    else if (e < m2) m2 = e;
+                }
+                const uint32_t w1 = wave_min_u32(m1);
+                const uint32_t w2 = wave_min_u32(m1 == w1 ? m2 : m1);   // (events are distinct)
+                rx = w1, ry = w2, rs = best;
+            }
+        }
+    }
+    if (lane == 0 && q < a.n) {
+        a.x[q] = rx;
+        a.y[q] = ry;
+        a.seq[q] = rs;
+    }
+}
+
+__global__ __launch_bounds__(kAncThreads) void k_anc_fork_flag(AncForkListArgs a, uint64_t n) {
+    const uint64_t q = (uint64_t)blockIdx.x * kAncThreads + threadIdx.x;
+    if (q <= n) a.flag[q] = q < n && a.x[q] != LX_ANC_NONE;
+}
+
+__global__ __launch_bounds__(kAncThreads) void k_anc_fork_scatter(AncForkListArgs a, uint64_t n) {
+    const uint64_t q = (uint64_t)blockIdx.x * kAncThreads + threadIdx.x;
+    if (q < a.n_heads) a.n_found[q] = a.off[(q + 1) * a.n_cheat] - a.off[q * a.n_cheat];
+    if (q >= n || !a.flag[q]) return;
+    const uint64_t pos = a.base + a.off[q];
+    a.out_creator[pos] = a.cheat_creator[q % a.n_cheat];
+    a.out_x[pos] = a.x[q];
+    a.out_y[pos] = a.y[q];
+    a.out_seq[pos] = a.seq[q];
+}
+
 }  // namespace
+
+hipError_t launch_anc_fork(const AncForkArgs &a, hipStream_t s) {
+    if (!a.n) return hipSuccess;
+    const uint64_t blocks = (a.n + kAncForkWaves - 1) / kAncForkWaves;
+    if (blocks > 0x7FFFFFFFull || (!a.creator && !a.n_cheat)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_anc_fork, dim3((uint32_t)blocks), dim3(kAncThreads), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_anc_fork_list(const AncForkListArgs &a, void *tmp, size_t tmp_bytes, hipStream_t s) {
+    const uint64_t n = (uint64_t)a.n_heads * a.n_cheat;
+    if (!n) return hipSuccess;
+    if (n + 1 > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    const dim3 grid((uint32_t)((n + 1 + kAncThreads - 1) / kAncThreads)), block(kAncThreads);
+    hipLaunchKernelGGL(k_anc_fork_flag, grid, block, 0, s, a, n);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    size_t tb = tmp_bytes;
+    e = hipcub::DeviceScan::ExclusiveSum(tmp, tb, a.flag, a.off, (int)(n + 1), s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_anc_fork_scatter, grid, block, 0, s, a, n);
+    return hipGetLastError();
+}
 
 hipError_t launch_anc_pairs(const AncPairArgs &a, hipStream_t s) {
     if (!a.n) return hipSuccess;

@@ -3418,6 +3418,9 @@ int lx_index_peek(lx_index *h, IndexView *o) {
     o->cheat_of = h->lay.cheat_of;
     o->cheat_off = h->lay.cheat_off;
     o->cheat_br = h->lay.cheat_br;
+    o->cheat_creator = h->lay.cheat_creator;
+    o->n_cheat = h->n_cheat;
+    o->branch_len = h->lay.branch_len;
     o->weights = &h->weights;
     o->by_creator = &h->by_creator;
     o->shard_count = h->shard_count;

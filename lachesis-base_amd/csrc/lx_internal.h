@@ -633,6 +633,39 @@ struct AncArgs {
     uint32_t out_cap;
     uint32_t *n_new;             // [H] of this launch
 };
+// Fork evidence: one wave per (head, creator) query.  Pairwise (head / creator
+// both [n]) or the grid of lx_anc_cheaters (creator = NULL): query q asks head
+// [q / n_cheat] about the cheat_creator[q % n_cheat].
+constexpr uint32_t kAncForkMaxBr = 1024;       // branches of one creator: their intervals stay in LDS
+constexpr uint32_t kAncForkWaves = kAncThreads / 64;
+struct AncForkArgs {
+    const uint32_t *hb, *la;
+    uint64_t stride;
+    const uint32_t *ev_branch, *ev_seq;
+    const uint32_t *brow;        // [branch * s_cap + seq - branch_first[branch]] -> event
+    const uint32_t *branch_first, *branch_len;
+    uint32_t s_cap;
+    const int32_t *cheat_of;     // creator -> cheater index (-1: one branch); CSR as IndexView
+    const uint32_t *cheat_off, *cheat_br;
+    const uint32_t *cheat_creator;   // cheater index -> creator, ascending
+    uint32_t n_cheat;
+    const uint32_t *head;        // pairwise [n]; grid [n / n_cheat]
+    const uint32_t *creator;     // pairwise [n]; grid NULL
+    uint64_t n;                  // queries
+    uint32_t *x, *y, *seq;       // [n]: the canonical pair and its seq, or LX_ANC_NONE, LX_ANC_NONE, 0
+};
+// The ordered list of one grid launch of n_heads heads: flag[q] = query q has
+// evidence (flag[n] = 0), off its exclusive prefix sums, `base` entries of the
+// call's earlier launches are in the list already.
+struct AncForkListArgs {
+    const uint32_t *x, *y, *seq; // [n] of the grid launch
+    const uint32_t *cheat_creator;
+    uint32_t n_cheat, n_heads;
+    uint32_t *flag, *off;        // [n + 1]
+    uint64_t base;
+    uint32_t *out_creator, *out_x, *out_y, *out_seq;   // [base + found]
+    uint32_t *n_found;           // [n_heads]
+};
 
 // ---- batched abft caller (lx_abft_kernels.hip, lx_abft.cpp)
 // lx_abft_build_frames: n candidate events that are not added.  Candidate c is
@@ -900,6 +933,9 @@ hipError_t anc_scan_bytes(uint32_t n, size_t *bytes);
 // count, scan and scatter of one confirm launch (lx_ancestry.hip)
 hipError_t launch_anc_confirm(const AncArgs &a, void *tmp, size_t tmp_bytes, hipStream_t s);
 hipError_t launch_anc_low(const uint32_t *labels, uint32_t lo, uint32_t hi, uint32_t *low, hipStream_t s);
+hipError_t launch_anc_fork(const AncForkArgs &a, hipStream_t s);
+// flags, scan and compaction of one grid launch into the ordered list
+hipError_t launch_anc_fork_list(const AncForkListArgs &a, void *tmp, size_t tmp_bytes, hipStream_t s);
 uint32_t root_fc_splits(uint32_t n_cand, uint32_t n_roots, uint32_t ncols);
 hipError_t launch_root_fc(const RootFcArgs &a, bool forks, bool seq16, hipStream_t s);
 uint32_t root_fc_blocks(const RootFcArgs &a);
@@ -944,10 +980,13 @@ struct IndexView {
     const uint32_t *ev_creator;
     const uint32_t *brow;        // [branch * s_cap + seq - branch_first[branch]] -> event
     const uint32_t *branch_first;
+    const uint32_t *branch_len;  // events on each branch
     uint32_t s_cap;
     const int32_t *cheat_of;     // creator -> cheater index (-1: one branch); CSR over all
     const uint32_t *cheat_off;   // branches of each cheater, original first (as GetArgs)
     const uint32_t *cheat_br;
+    const uint32_t *cheat_creator;   // cheater index -> creator, ascending
+    uint32_t n_cheat;
     const std::vector<uint32_t> *weights;
     const std::vector<std::vector<uint32_t>> *by_creator;
     uint32_t shard_count;

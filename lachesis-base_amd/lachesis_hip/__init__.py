@@ -18,7 +18,8 @@ vecfc/forkless_cause_test.go:
 * :mod:`mediantime`   -- vecmt's MedianTime / merged HighestBeforeTime over
   include/lachesis_mediantime.h (:class:`MedianTimeIndex`)
 * :mod:`ancestry`     -- DfsSubgraph / confirmEvents as scans of the vector clock
-  over include/lachesis_ancestry.h (:class:`AncestryIndex`)
+  over include/lachesis_ancestry.h (:class:`AncestryIndex`), and fork
+  evidence: the two events behind each cheater a head observes
 * :mod:`abft`         -- abft.IndexedLachesis over include/lachesis_abft.h:
   frames, roots, election, blocks with batched ForklessCause on the GPU
 

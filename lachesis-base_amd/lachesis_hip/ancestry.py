@@ -9,6 +9,10 @@ scan over the epoch's events on the device
 (lachesis-base_amd/csrc/lx_ancestry.{cpp,hip}).  :class:`AncestryIndex` keeps
 one label per event, e.g. the frame that confirmed it.
 
+Fork evidence: where a head sees a creator as a cheater, ``fork_pairs`` /
+``cheaters`` name the two events that prove it -- the two lowest events of that
+creator, at the lowest seq, that share a seq and are both observed by the head.
+
 Like :class:`lachesis_hip.mediantime.MedianTimeIndex` this module only keeps
 the event-ID -> dense-index map of the :class:`VecfcIndex` it is built on.
 """
@@ -18,6 +22,8 @@ import ctypes
 import numpy as np
 
 from .capi import LxError, _p, u8p, u32p, vp
+
+NONE = 0xFFFFFFFF   # LX_ANC_NONE: no event
 
 
 class AncestryIndex:
@@ -110,6 +116,43 @@ class AncestryIndex:
         self._chk(self.L.lx_anc_low_water(self.h, ctypes.byref(ev)))
         return ev.value
 
+    def fork_pairs_dense(self, heads, creators):
+        """lx_anc_fork_pairs: arrays ``(x, y, seq)``, pairwise for (heads[i],
+        creators[i]); ``x < y`` the canonical pair of events of that creator
+        (validator idx) with equal seq that the head observes, or
+        ``(NONE, NONE, 0)``."""
+        heads = np.ascontiguousarray(heads, dtype=np.uint32)
+        creators = np.ascontiguousarray(creators, dtype=np.uint32)
+        if len(heads) != len(creators):
+            raise ValueError("one creator per head")
+        n = len(heads)
+        x, y, seq = (np.zeros(max(n, 1), dtype=np.uint32) for _ in range(3))
+        if n:
+            self._chk(self.L.lx_anc_fork_pairs(self.h, n, _p(heads, u32p), _p(creators, u32p), _p(x, u32p),
+                                               _p(y, u32p), _p(seq, u32p)))
+        return x[:n], y[:n], seq[:n]
+
+    def last_cheaters_dense(self):
+        """The list of the last lx_anc_cheaters: arrays (creator, x, y, seq)."""
+        n = ctypes.c_uint64()
+        self._chk(self.L.lx_anc_last_cheaters(self.h, None, None, None, None, 0, ctypes.byref(n)))
+        c, x, y, s = (np.zeros(max(n.value, 1), dtype=np.uint32) for _ in range(4))
+        self._chk(self.L.lx_anc_last_cheaters(self.h, _p(c, u32p), _p(x, u32p), _p(y, u32p), _p(s, u32p), n.value,
+                                              ctypes.byref(n)))
+        return c[:n.value], x[:n.value], y[:n.value], s[:n.value]
+
+    def cheaters_dense(self, heads):
+        """lx_anc_cheaters: per head, in call order, the list of ``(creator, x,
+        y, seq)`` of every cheater it observes, ascending creator idx."""
+        heads = np.ascontiguousarray(heads, dtype=np.uint32)
+        n_found = np.zeros(max(len(heads), 1), dtype=np.uint32)
+        self._chk(self.L.lx_anc_cheaters(self.h, len(heads), _p(heads, u32p), _p(n_found, u32p)))
+        c, x, y, s = self.last_cheaters_dense()
+        cuts = np.cumsum(n_found[:len(heads)], dtype=np.uint64)
+        assert (int(cuts[-1]) if len(cuts) else 0) == len(c)
+        rows = list(zip((int(v) for v in c), (int(v) for v in x), (int(v) for v in y), (int(v) for v in s)))
+        return [rows[int(a):int(b)] for a, b in zip([0] + list(cuts[:-1]), cuts)]
+
     # event IDs ---------------------------------------------------------------
     def observes(self, heads, xs):
         """``heads`` / ``xs``: events or their IDs, pairwise."""
@@ -138,3 +181,16 @@ class AncestryIndex:
                 hi += 1
             self.set_labels_dense(idx[lo], [at[i] for i in idx[lo:hi]])
             lo = hi
+
+    def fork_pairs(self, heads, creators):
+        """``heads``: events or IDs, ``creators``: validator idxs, pairwise.
+        Per pair ``(event ID, event ID, seq)`` or ``None``."""
+        ids = self.dagi.ids
+        x, y, seq = self.fork_pairs_dense(self._dense(heads), creators)
+        return [None if int(a) == NONE else (ids[int(a)], ids[int(b)], int(s)) for a, b, s in zip(x, y, seq)]
+
+    def cheaters(self, heads):
+        """Per head (event or ID) the list of ``(creator idx, event ID, event
+        ID, seq)`` of every cheater it observes."""
+        ids = self.dagi.ids
+        return [[(c, ids[a], ids[b], s) for c, a, b, s in g] for g in self.cheaters_dense(self._dense(heads))]

@@ -163,6 +163,9 @@ SIGNATURES = [
     ("lx_anc_labels", ctypes.c_int, [vp, ctypes.c_uint64, ctypes.c_uint64, u32p]),
     ("lx_anc_set_labels", ctypes.c_int, [vp, ctypes.c_uint64, ctypes.c_uint64, u32p]),
     ("lx_anc_low_water", ctypes.c_int, [vp, u64p]),
+    ("lx_anc_fork_pairs", ctypes.c_int, [vp, ctypes.c_uint64, u32p, u32p, u32p, u32p, u32p]),
+    ("lx_anc_cheaters", ctypes.c_int, [vp, ctypes.c_uint32, u32p, u32p]),
+    ("lx_anc_last_cheaters", ctypes.c_int, [vp, u32p, u32p, u32p, u32p, ctypes.c_uint64, u64p]),
     # include/lachesis_batcher.h
     ("lx_batcher_create", ctypes.c_int, [ctypes.POINTER(vp)]),
     ("lx_batcher_destroy", None, [vp]),
