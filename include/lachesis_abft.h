@@ -220,8 +220,72 @@ int lx_abft_build_frames(lx_abft *a, uint32_t n, const uint32_t *creator_idx, co
                          const uint64_t *parent_off, const uint32_t *parent_idx,
                          uint32_t *out_frame, uint8_t *out_is_root, uint32_t *err_index);
 
-/* GPU work of the last lx_abft_build_frames (zeros after a call that failed
- * its input checks or had n == 0). */
+/* Frame progress of candidate events that are NOT added: how far each is from
+ * the next frame.  All quantities are those of the index with the candidate
+ * added (what Add would produce: DESIGN.md sections 9c, 9d).
+ *   stake(e, r)  0 if HighestBefore(e)[branch(r)] is a fork marker, otherwise
+ *                the weight of the distinct creators c with a branch j where
+ *                LowestAfter(r)[j] != 0 && LowestAfter(r)[j] <= HighestBefore(e)[j].Seq
+ *                -- the WeightCounter of forklessCause before HasQuorum:
+ *                ForklessCause(e, r) <=> stake(e, r) >= quorum.
+ * Per frame f, over the engine's root slots of f in its order, a slot whose
+ * event is e itself left out of the three sums:
+ *   out_n_roots    the slots of f (own slot included)
+ *   out_n_caused   the slots with stake(e, r) >= quorum
+ *   out_stake      the weight of the distinct creators of those slots (the
+ *                  counter of forklessCausedByQuorumOn without its break)
+ *   out_root_stake the sum over the slots of min(stake(e, r), quorum)
+ * Frame asked: at_frame == NULL or an entry LX_FRAME_BUILD asks candidate i at
+ * its Build frame, the value lx_abft_build_frames returns; there out_stake <
+ * quorum, unless the Build cap of 100 frames stopped the loop or the candidate
+ * has no self-parent (frame 1 is given without asking roots(1); its progress
+ * over roots(1) is reported as it is).  An entry f >= 1 asks frame f alone, no
+ * frame loop; a frame without roots answers zeros.  out_frame[i] = the frame
+ * the numbers are about.  Every out_* is optional except out_frame.
+ * flags: LX_PROGRESS_PAIRS keeps stake(e, r) of every slot for
+ * lx_abft_last_progress_pairs.
+ *
+ * Reads only, with the guarantee of lx_abft_build_frames: no event added, no
+ * root slot, no election, no callback, no rollback counted; lx_mt and lx_anc
+ * handles keep what they hold; the stats of lx_abft_last_stats stay those of
+ * the last lx_abft_process_batch.
+ * Inputs, checks and refusals are those of lx_abft_build_frames, all before
+ * any device work, plus LX_ERR_ARG for an at_frame entry 0 and for unknown
+ * flag bits; *err_index (optional) receives the first offending candidate.
+ * n == 0 is ok and launches nothing. */
+#define LX_PROGRESS_PAIRS 1u   /* keep the per-pair stakes for lx_abft_last_progress_pairs */
+int lx_abft_build_progress(lx_abft *a, uint32_t n, const uint32_t *creator_idx, const uint32_t *seq,
+                           const uint64_t *parent_off, const uint32_t *parent_idx,
+                           const uint32_t *at_frame, uint32_t flags,
+                           uint32_t *out_frame, uint32_t *out_n_roots, uint32_t *out_n_caused,
+                           uint32_t *out_stake, uint64_t *out_root_stake, uint32_t *err_index);
+
+/* The same for n indexed events (any event of the epoch, not flushed ones
+ * included), on the index as it stands.  LX_FRAME_BUILD asks an event at its
+ * own frame: there out_stake < quorum, and at each earlier frame back to its
+ * self-parent's frame out_stake >= quorum.  An event that is a root of the
+ * frame asked leaves its own slot out of the three sums and keeps it in the
+ * pair list.  Reads only, as above.  LX_ERR_STATE: not bootstrapped.
+ * LX_ERR_ARG: an event >= lx_num_events, an at_frame entry 0, unknown flags. */
+int lx_abft_event_progress(lx_abft *a, uint32_t n, const uint32_t *ev, const uint32_t *at_frame,
+                           uint32_t flags, uint32_t *out_frame, uint32_t *out_n_roots,
+                           uint32_t *out_n_caused, uint32_t *out_stake, uint64_t *out_root_stake,
+                           uint32_t *err_index);
+
+/* Per-pair stakes of the last progress call made with LX_PROGRESS_PAIRS:
+ * entry i owns [pair_off[i], pair_off[i+1]) (n + 1 offsets), one entry per
+ * slot of its frame in slot order, own slot included: the root event and
+ * stake(e, r).  *n_pairs = their number; the first min(cap, *n_pairs) are
+ * written.  Any pointer but n_pairs may be NULL.  Empty (pair_off[0] = 0,
+ * *n_pairs = 0) after any other call that launches work on the handle, a
+ * progress call without the flag or a failed one included. */
+int lx_abft_last_progress_pairs(lx_abft *a, uint64_t *pair_off, uint32_t *out_root,
+                                uint32_t *out_stake, uint64_t cap, uint64_t *n_pairs);
+
+/* GPU work of the last lx_abft_build_frames, lx_abft_build_progress or
+ * lx_abft_event_progress, whichever came last (zeros after a call that failed
+ * its input checks or had n == 0); in a progress call k_root_progress takes
+ * the place of the quorum kernel. */
 typedef struct lx_abft_build_stats {
     uint32_t launches;      /* kernel launches: uploads, k_build_rows, root-FC and quorum per round */
     uint32_t frame_steps;   /* (frame, round) steps evaluated */

@@ -237,12 +237,26 @@ struct lx_abft {
     DVec<VoteArgs> ea_args;               // ... launch args, grouped by round
     DVec<RootFcArgs> d_fcargs;            // merged frame steps of a claimed batch: per-step args
     DVec<QuorumArgs> d_qargs;
+    DVec<ProgressArgs> d_pgargs;          // lx_abft_build_progress / lx_abft_event_progress: per-step args
     // lx_abft_build_frames: the scratch plane of virtual rows, the per-candidate
     // tables, bit rows nobody reads, the NONE list k_root_quorum takes as events
     DVec<uint32_t> b_plane, b_tab, b_bits, b_none;
     DVec<BuildArgs> b_args;             // the tables' pointers as the OWN kernels read them
     uint64_t b_none_n = 0;              // entries of b_none written
     lx_abft_build_stats bstats{};
+    // the progress calls: k_root_progress records and pair stakes of one round
+    // (pinned, device-mapped), and the pair stakes kept for
+    // lx_abft_last_progress_pairs -- rows in the order their candidates stopped
+    uint4 *pg_pin = nullptr;
+    uint64_t pg_pin_cap = 0;
+    uint32_t *pp_pin = nullptr;
+    uint64_t pp_pin_cap = 0;
+    struct PairEnt {
+        uint64_t off;                   // into pp_keep
+        uint32_t n, frame;              // slots of the frame asked
+    };
+    std::vector<PairEnt> pp_ent;        // per entry of the call
+    std::vector<uint32_t> pp_keep;
     uint32_t n_k = 0;
     uint64_t k_gen = 0;                 // branch_gen the cheater columns were built for; 0 = stale
     std::vector<uint32_t> h_row;
@@ -641,18 +655,24 @@ struct FcStep {
     const uint32_t *cand;
     uint32_t n_cand, n_roots, words;
     uint64_t row0, qoff;
+    uint64_t pair0 = 0;   // progress steps that keep the pair stakes: the step's first word
 };
 
 // lx_abft_build_frames: the steps' candidates are not events but rows of a
 // scratch plane of virtual HighestBefore rows (FcStep::cand = row numbers,
 // FcStep::row0 counts from `bits`)
 struct BuildSteps {
-    const uint32_t *plane;
+    const uint32_t *plane;   // NULL: lx_abft_event_progress -- indexed events, the index's HB plane, the plain kernels
     const uint32_t *none;    // LX_NONE per candidate: no candidate is a root slot
     uint32_t *bits;
     const BuildArgs *args;   // the own-creator term's tables, on the device
     const BuildRowsArgs *rows;   // first round: k_build_rows goes between the uploads and the first step
     bool seq16;              // the candidates' own seqs fit 16 bits
+    // the progress calls (k_root_progress in place of k_root_quorum): a record
+    // per candidate at prog_out + FcStep::qoff, the pair stakes (or NULL) at
+    // prog_pairs + FcStep::pair0; both device-mapped pinned memory
+    uint4 *prog_out;
+    uint32_t *prog_pairs;
 };
 
 // Many steps in one k_root_fc and one k_root_quorum launch (the MULTI forms;
@@ -679,10 +699,13 @@ int launch_fc_steps(lx_abft *a, const IndexView &iv, const std::vector<FcStep> &
     ARC(reserve(a, a->d_cand, ncand, 0, s));
     ARC(reserve(a, a->d_psum, npsum, 0, s));
     ARC(reserve(a, a->d_fcargs, st.size(), 0, s));
-    ARC(reserve(a, a->d_qargs, st.size(), 0, s));
+    const bool prog = own && own->prog_out;
+    if (prog) ARC(reserve(a, a->d_pgargs, st.size(), 0, s));
+    else ARC(reserve(a, a->d_qargs, st.size(), 0, s));
     ARC(refresh_cheaters(a, iv));
     std::vector<RootFcArgs> fa(st.size());
-    std::vector<QuorumArgs> qa(st.size());
+    std::vector<QuorumArgs> qa(prog ? 0 : st.size());
+    std::vector<ProgressArgs> pa(prog ? st.size() : 0);
     uint64_t coff = 0, poff = 0, pairs = 0;
     uint32_t blocks = 0, qblocks = 0;
     for (size_t j = 0; j < st.size(); j++) {
@@ -690,14 +713,14 @@ int launch_fc_steps(lx_abft *a, const IndexView &iv, const std::vector<FcStep> &
         Frame &fr = a->frames[x.frame];
         a->up.add(a->d_cand.p + coff, x.cand, x.n_cand * 4ull);
         RootFcArgs &r = fa[j];
-        r.hb = own ? own->plane : iv.hb;
+        r.hb = own && own->plane ? own->plane : iv.hb;
         r.la = iv.la;
         r.stride = iv.stride;
         r.cand = a->d_cand.p + coff;
         r.n_cand = x.n_cand;
         r.roots = fr.d_ev.p;
         r.n_roots = x.n_roots;
-        r.roots_fallback = own ? fr.ev[0] : x.cand[0];
+        r.roots_fallback = own && own->plane ? fr.ev[0] : x.cand[0];
         r.ncols = ncols;
         r.wpad = iv.wpad;
         r.quorum = a->quorum;
@@ -713,21 +736,40 @@ int launch_fc_steps(lx_abft *a, const IndexView &iv, const std::vector<FcStep> &
         r.block0 = blocks;
         r.own = own ? own->args : nullptr;
         blocks += lx::root_fc_blocks(r);
-        QuorumArgs &q = qa[j];
-        q.psum = r.psum;
-        q.n_split = n_split;
-        q.bits = (own ? own->bits : a->arena.p) + x.row0;
-        q.words = x.words;
-        q.n_roots = x.n_roots;
-        q.n_cand = x.n_cand;
-        q.cand = own ? own->none : r.cand;
-        q.root_ev = fr.d_ev.p;
-        q.creator = fr.d_creator.p;
-        q.dup = fr.d_dup.p;
-        q.wcreator = iv.wpad;
-        q.quorum = a->quorum;
-        q.q = q_dev + x.qoff;
-        q.block0 = qblocks;
+        if (prog) {
+            ProgressArgs &q = pa[j];
+            q.psum = r.psum;
+            q.n_split = n_split;
+            q.words = x.words;
+            q.n_roots = x.n_roots;
+            q.n_cand = x.n_cand;
+            q.cand = own->plane ? own->none : r.cand;
+            q.root_ev = fr.d_ev.p;
+            q.creator = fr.d_creator.p;
+            q.dup = fr.d_dup.p;
+            q.wcreator = iv.wpad;
+            q.quorum = a->quorum;
+            q.q = q_dev + x.qoff;
+            q.out = own->prog_out + x.qoff;
+            q.pairs = own->prog_pairs ? own->prog_pairs + x.pair0 : nullptr;
+            q.block0 = qblocks;
+        } else {
+            QuorumArgs &q = qa[j];
+            q.psum = r.psum;
+            q.n_split = n_split;
+            q.bits = (own ? own->bits : a->arena.p) + x.row0;
+            q.words = x.words;
+            q.n_roots = x.n_roots;
+            q.n_cand = x.n_cand;
+            q.cand = own ? own->none : r.cand;
+            q.root_ev = fr.d_ev.p;
+            q.creator = fr.d_creator.p;
+            q.dup = fr.d_dup.p;
+            q.wcreator = iv.wpad;
+            q.quorum = a->quorum;
+            q.q = q_dev + x.qoff;
+            q.block0 = qblocks;
+        }
         qblocks += (x.n_cand + 3) / 4;
         coff += x.n_cand;
         poff += (uint64_t)n_split * x.n_cand * x.words * 32;
@@ -738,7 +780,8 @@ int launch_fc_steps(lx_abft *a, const IndexView &iv, const std::vector<FcStep> &
         a->stats.fc_pair_cols += pairs * iv.V;
     }
     a->up.add(a->d_fcargs.p, fa.data(), fa.size() * sizeof(RootFcArgs));
-    a->up.add(a->d_qargs.p, qa.data(), qa.size() * sizeof(QuorumArgs));
+    if (!prog) a->up.add(a->d_qargs.p, qa.data(), qa.size() * sizeof(QuorumArgs));
+    else if (pa.size() > 1) a->up.add(a->d_pgargs.p, pa.data(), pa.size() * sizeof(ProgressArgs));
     if (pt) pt->mark("args");
     ARC(flush_uploads(a, s));
     if (pt) pt->mark("upload");
@@ -748,8 +791,13 @@ int launch_fc_steps(lx_abft *a, const IndexView &iv, const std::vector<FcStep> &
             AHIP(a, lx::launch_build_rows(*own->rows, forks, s));
             a->bstats.launches++;
         }
-        AHIP(a, lx::launch_root_fc_own_multi(a->d_fcargs.p, (uint32_t)st.size(), blocks, forks, seq16, s));
-        AHIP(a, lx::launch_root_quorum_multi(a->d_qargs.p, (uint32_t)st.size(), qblocks, s));
+        if (own->plane)
+            AHIP(a, lx::launch_root_fc_own_multi(a->d_fcargs.p, (uint32_t)st.size(), blocks, forks, seq16, s));
+        else
+            AHIP(a, lx::launch_root_fc_multi(a->d_fcargs.p, (uint32_t)st.size(), blocks, forks, seq16, s));
+        if (!prog) AHIP(a, lx::launch_root_quorum_multi(a->d_qargs.p, (uint32_t)st.size(), qblocks, s));
+        else if (pa.size() > 1) AHIP(a, lx::launch_root_progress_multi(a->d_pgargs.p, (uint32_t)pa.size(), qblocks, s));
+        else AHIP(a, lx::launch_root_progress(pa[0], s));   // one step: its args by value
         a->bstats.launches += 2;
         a->bstats.fc_pairs += pairs;
         a->bstats.fc16 = !forks && seq16;
@@ -1802,28 +1850,71 @@ int process_pass(lx_abft *a, uint32_t n, const uint32_t *creator, const uint32_t
 // merged launch, one wait per round.  Nothing of the engine's state is
 // written: the frames' device mirrors are completed (sync_frame), scratch
 // buffers grow, and that is all.
+// lx_abft_build_progress / lx_abft_event_progress (section 9d) are the same
+// steps with k_root_progress in the place of k_root_quorum: the stake sums of
+// the step on which an entry stops are reported, not only its frame.
 struct BuildCand {
     uint32_t pos;      // position in the call
     uint32_t spf;      // selfParentFrame
     uint32_t f;        // the loop's current frame
+    bool last;         // progress calls: asked at f alone, no climb (explicit frame, cap reached, no self-parent, event)
 };
 
-int build_frames(lx_abft *a, uint32_t n, const uint32_t *creator, const uint32_t *seq, const uint64_t *poff,
-                 const uint32_t *par, uint32_t *out_frame, uint8_t *out_is_root, uint32_t *err_index) {
-    IndexView iv;
-    int rc = lx_index_peek(a->ix, &iv);
-    if (rc) return a->ixfail(rc);
-    IndexHostMeta hm;
-    if ((rc = lx_index_host_meta(a->ix, &hm))) return a->ixfail(rc);
-    const uint64_t n_ev = std::min<uint64_t>(iv.n_events, a->ev_frame.size());
+// What a progress call wants beyond the frames (lx_abft_build_progress,
+// lx_abft_event_progress).  Any out pointer may be NULL.
+struct Progress {
+    const uint32_t *events;   // lx_abft_event_progress: entry k is indexed event events[k]; NULL: candidates
+    const uint32_t *at_frame; // per entry: LX_FRAME_BUILD or the frame to ask; NULL: LX_FRAME_BUILD
+    bool pairs;               // LX_PROGRESS_PAIRS
+    uint32_t *n_roots, *n_caused, *stake;
+    uint64_t *root_stake;
+};
+
+// pinned, device-mapped scratch of the progress calls (contents not kept)
+template <typename T>
+int pin_buffer(lx_abft *a, T **pin, uint64_t *cap, uint64_t n, hipStream_t s, T **dev) {
+    if (n > *cap) {
+        if (*pin) {
+            AHIP(a, hipStreamSynchronize(s));
+            (void)hipHostFree(*pin);
+        }
+        *pin = nullptr;
+        *cap = 0;
+        const uint64_t want = std::max<uint64_t>(n + n / 2, 4096);
+        AHIP(a, hipHostMalloc((void **)pin, want * sizeof(T), hipHostMallocMapped));
+        *cap = want;
+    }
+    void *d = nullptr;
+    AHIP(a, hipHostGetDevicePointer(&d, *pin, 0));
+    *dev = static_cast<T *>(d);
+    return 0;
+}
+
+void clear_pairs(lx_abft *a) {
+    a->pp_ent.clear();
+    a->pp_keep.clear();
+}
+
+// The candidates' tables as the device reads them (BuildArgs), after the input
+// checks of lx_abft_build_frames on host tables alone.  act: the candidates
+// that ask anything, = rows of the scratch plane, in call order.  pg == NULL
+// (lx_abft_build_frames): a candidate without a self-parent asks nothing; a
+// progress call gives it a virtual row too (own branch = the creator's
+// original column, seq 1) and asks roots(1).
+struct BuildTables {
+    std::vector<BuildCand> act;
+    std::vector<uint32_t> br, seq, cr, poff{0}, par;
+    uint32_t max_seq = 0;
+};
+
+int build_tables(lx_abft *a, const IndexHostMeta &hm, uint64_t n_ev, uint32_t n, const uint32_t *creator,
+                 const uint32_t *seq, const uint64_t *poff, const uint32_t *par, const Progress *pg,
+                 uint32_t *err_index, BuildTables *t) {
     auto bad = [&](uint32_t i, const char *what) {
         if (err_index) *err_index = i;
         return a->fail(LX_ERR_ARG, "candidate %u: %s", i, what);
     };
-    // ---- input checks (host tables only)
-    std::vector<BuildCand> act;
-    std::vector<uint32_t> tab_br, tab_seq, tab_cr, tab_poff{0}, tab_par, srt;
-    uint32_t cand_max_seq = 0;
+    std::vector<uint32_t> srt;
     for (uint32_t i = 0; i < n; i++) {
         const uint32_t c = creator[i], s = seq[i];
         if (c >= a->V) return bad(i, "creator out of range");
@@ -1836,45 +1927,49 @@ int build_frames(lx_abft *a, uint32_t n, const uint32_t *creator, const uint32_t
         srt.assign(par + p0, par + p1);
         std::sort(srt.begin(), srt.end());
         if (std::adjacent_find(srt.begin(), srt.end()) != srt.end()) return bad(i, "duplicate parent");
+        const uint32_t at = pg && pg->at_frame ? pg->at_frame[i] : LX_FRAME_BUILD;
+        if (at == 0) return bad(i, "at_frame 0");
         const bool own_first = p1 > p0 && hm.ev_creator[par[p0]] == c;
+        uint32_t br = c, spf = 0;
         if (s == 1) {
             if (own_first) return bad(i, "seq 1 with a self-parent");
             if (hm.branch_len[c]) return bad(i, "would open a new branch (the creator has events); use lx_abft_build");
-            continue;   // no self-parent: f = 0, roots(0) is empty -> frame 1
+            if (!pg) continue;   // no self-parent: f = 0, roots(0) is empty -> frame 1
+        } else {
+            if (!own_first || hm.ev_seq[par[p0]] != s - 1) return bad(i, "no self-parent of the same creator at seq - 1");
+            const uint32_t sp = par[p0];
+            br = hm.ev_branch[sp];
+            if (hm.branch_first[br] + hm.branch_len[br] - 1 != s - 1)
+                return bad(i, "would open a new branch (the self-parent is not its branch's last event); use lx_abft_build");
+            spf = a->ev_frame[sp];
         }
-        if (!own_first || hm.ev_seq[par[p0]] != s - 1) return bad(i, "no self-parent of the same creator at seq - 1");
-        const uint32_t sp = par[p0], br = hm.ev_branch[sp];
-        if (hm.branch_first[br] + hm.branch_len[br] - 1 != s - 1)
-            return bad(i, "would open a new branch (the self-parent is not its branch's last event); use lx_abft_build");
-        if ((uint64_t)tab_par.size() + (p1 - p0) > 0xFFFFFFFFull) return bad(i, "too many parents");
-        const uint32_t spf = a->ev_frame[sp];
-        act.push_back(BuildCand{i, spf, spf});
-        tab_br.push_back(br);
-        tab_seq.push_back(s);
-        tab_cr.push_back(c);
-        tab_par.insert(tab_par.end(), par + p0, par + p1);
-        tab_poff.push_back((uint32_t)tab_par.size());
-        cand_max_seq = std::max(cand_max_seq, s);
+        if ((uint64_t)t->par.size() + (p1 - p0) > 0xFFFFFFFFull) return bad(i, "too many parents");
+        if (at != LX_FRAME_BUILD) t->act.push_back(BuildCand{i, spf, at, true});
+        else if (s == 1) t->act.push_back(BuildCand{i, 0, 1, true});
+        else t->act.push_back(BuildCand{i, spf, spf, false});
+        t->br.push_back(br);
+        t->seq.push_back(s);
+        t->cr.push_back(c);
+        t->par.insert(t->par.end(), par + p0, par + p1);
+        t->poff.push_back((uint32_t)t->par.size());
+        t->max_seq = std::max(t->max_seq, s);
     }
-    for (uint32_t i = 0; i < n; i++) {
-        out_frame[i] = 1;
-        if (out_is_root) out_is_root[i] = 1;
-    }
-    const uint32_t m = (uint32_t)act.size();
-    if (!m) return 0;
+    return 0;
+}
 
-    // ---- the virtual rows
-    if ((rc = lx_index_view(a->ix, &iv))) return a->ixfail(rc);   // the pending small-batch run is in the planes
-    if (iv.shard_count > 1 || iv.loading) return a->fail(LX_ERR_STATE, "abft needs an unsharded, loaded index");
+// The virtual rows: the tables go up with the first round's steps, k_build_rows
+// runs ahead of them (BuildSteps::rows).  ra must outlive the first round.
+int build_plane(lx_abft *a, const IndexView &iv, const BuildTables &t, BuildSteps *own, BuildRowsArgs *ra) {
     hipStream_t s = iv.stream;
+    const uint32_t m = (uint32_t)t.act.size();
     ARC(reserve(a, a->b_plane, (uint64_t)m * iv.stride, 0, s));
     const uint64_t o_seq = m, o_cr = 2ull * m, o_poff = 3ull * m, o_par = 4ull * m + 1;
-    ARC(reserve(a, a->b_tab, o_par + tab_par.size(), 0, s));
-    a->up.add(a->b_tab.p, tab_br.data(), m * 4ull);
-    a->up.add(a->b_tab.p + o_seq, tab_seq.data(), m * 4ull);
-    a->up.add(a->b_tab.p + o_cr, tab_cr.data(), m * 4ull);
-    a->up.add(a->b_tab.p + o_poff, tab_poff.data(), (m + 1) * 4ull);
-    a->up.add(a->b_tab.p + o_par, tab_par.data(), tab_par.size() * 4ull);
+    ARC(reserve(a, a->b_tab, o_par + t.par.size(), 0, s));
+    a->up.add(a->b_tab.p, t.br.data(), m * 4ull);
+    a->up.add(a->b_tab.p + o_seq, t.seq.data(), m * 4ull);
+    a->up.add(a->b_tab.p + o_cr, t.cr.data(), m * 4ull);
+    a->up.add(a->b_tab.p + o_poff, t.poff.data(), (m + 1) * 4ull);
+    a->up.add(a->b_tab.p + o_par, t.par.data(), t.par.size() * 4ull);
     if (a->b_none_n < m) {
         ARC(reserve(a, a->b_none, m, 0, s));
         const std::vector<uint32_t> none(a->b_none.cap, NONE);
@@ -1893,48 +1988,71 @@ int build_frames(lx_abft *a, uint32_t n, const uint32_t *creator, const uint32_t
     ba.cheat_br = iv.cheat_br;
     ARC(reserve(a, a->b_args, 1, 0, s));
     a->up.add(a->b_args.p, &ba, sizeof ba);
-    BuildSteps own{};
-    own.args = a->b_args.p;
-    own.plane = a->b_plane.p;
-    own.none = a->b_none.p;
-    own.seq16 = cand_max_seq <= 0xFFFFu;
-    BuildRowsArgs ra{};
-    ra.hb = iv.hb;
-    ra.stride = iv.stride;
-    ra.B = iv.B;
-    ra.plane = a->b_plane.p;
-    ra.n = m;
-    ra.c = ba;
-    ra.branch_first = iv.branch_first;
-    for (const auto &l : *iv.by_creator) ra.n_cheat += l.size() > 1;
-    const uint64_t up0 = a->up.launches;
-    own.rows = &ra;   // the tables, the first round's steps and candidates go up in one k_scatter launch
+    own->args = a->b_args.p;
+    own->plane = a->b_plane.p;
+    own->none = a->b_none.p;
+    own->seq16 = t.max_seq <= 0xFFFFu;
+    *ra = BuildRowsArgs{};
+    ra->hb = iv.hb;
+    ra->stride = iv.stride;
+    ra->B = iv.B;
+    ra->plane = a->b_plane.p;
+    ra->n = m;
+    ra->c = ba;
+    ra->branch_first = iv.branch_first;
+    for (const auto &l : *iv.by_creator) ra->n_cheat += l.size() > 1;
+    own->rows = ra;   // the tables, the first round's steps and candidates go up in one k_scatter launch
+    return 0;
+}
 
-    // ---- the frame loop, one wait per round
+// The frame loop of calcFrameIdx in rounds, one wait per round: every entry
+// still climbing asks q_f at its current frame, the entries of one frame are
+// one step of a merged launch.  Entry k is row k of the scratch plane, or
+// (pg->events) an indexed event.  pg: the numbers of the step on which an
+// entry stops are reported; an entry the Build cap stopped is asked once more
+// at the frame it got.
+int build_rounds(lx_abft *a, const IndexView &iv, std::vector<BuildCand> &act, BuildSteps &own, const Progress *pg) {
+    hipStream_t s = iv.stream;
+    const uint32_t m = (uint32_t)act.size();
     std::vector<uint32_t> live(m);
     for (uint32_t k = 0; k < m; k++) live[k] = k;
-    std::map<uint32_t, std::vector<uint32_t>> by_frame;
+    std::map<uint32_t, std::vector<uint32_t>> by_frame, ev_by_frame;
     std::vector<FcStep> st;
+    std::vector<const std::vector<uint32_t> *> st_ent;
     while (!live.empty()) {
         by_frame.clear();
         for (uint32_t k : live) by_frame[act[k].f].push_back(k);
+        if (pg && pg->events) {
+            ev_by_frame.clear();
+            for (uint32_t k : live) ev_by_frame[act[k].f].push_back(pg->events[act[k].pos]);
+        }
         st.clear();
-        uint64_t rows = 0, qn = 0;
+        st_ent.clear();
+        uint64_t rows = 0, qn = 0, pn = 0;
         for (auto &kv : by_frame) {
             const uint32_t f = kv.first;
             const uint32_t R = f < a->frames.size() ? (uint32_t)a->frames[f].ev.size() : 0;
             if (!R) continue;   // no roots: no quorum, the loop stops at f
             const uint32_t words = (R + 31) / 32, nc = (uint32_t)kv.second.size();
-            st.push_back(FcStep{f, kv.second.data(), nc, R, words, rows, qn});
-            rows += (uint64_t)nc * words;
+            const uint32_t *rows_of = pg && pg->events ? ev_by_frame[f].data() : kv.second.data();
+            st.push_back(FcStep{f, rows_of, nc, R, words, rows, qn, pn});
+            st_ent.push_back(&kv.second);
+            if (!pg) rows += (uint64_t)nc * words;
+            else if (pg->pairs) pn += (uint64_t)nc * R;
             qn += nc;
         }
         if (st.empty()) {
             ARC(flush_uploads(a, s));   // nothing asks: leave no upload pending
             break;
         }
-        ARC(reserve(a, a->b_bits, rows + 1, 0, s));
-        own.bits = a->b_bits.p;
+        if (pg) {
+            ARC(pin_buffer(a, &a->pg_pin, &a->pg_pin_cap, qn, s, &own.prog_out));
+            own.prog_pairs = nullptr;
+            if (pn) ARC(pin_buffer(a, &a->pp_pin, &a->pp_pin_cap, pn, s, &own.prog_pairs));
+        } else {
+            ARC(reserve(a, a->b_bits, rows + 1, 0, s));
+            own.bits = a->b_bits.p;
+        }
         uint8_t *q_dev = nullptr;
         ARC(q_buffer(a, qn, s, &q_dev));
         ARC(launch_fc_steps(a, iv, st, q_dev, nullptr, &own));
@@ -1943,19 +2061,111 @@ int build_frames(lx_abft *a, uint32_t n, const uint32_t *creator, const uint32_t
         a->bstats.frame_steps += (uint32_t)st.size();
         a->bstats.rounds++;
         live.clear();
-        for (const FcStep &x : st)
+        for (size_t i = 0; i < st.size(); i++) {
+            const FcStep &x = st[i];
             for (uint32_t j = 0; j < x.n_cand; j++) {
-                BuildCand &c = act[x.cand[j]];
-                if (!a->q_pin[x.qoff + j]) continue;
-                c.f++;
-                if (c.f < c.spf + kBuildCap) live.push_back(x.cand[j]);
+                const uint32_t k = (*st_ent[i])[j];
+                BuildCand &c = act[k];
+                if (a->q_pin[x.qoff + j] && !c.last) {
+                    c.f++;
+                    if (c.f >= c.spf + kBuildCap) c.last = true;
+                    if (!c.last || pg) {
+                        live.push_back(k);
+                        continue;
+                    }
+                }
+                if (!pg) continue;
+                const uint4 o = a->pg_pin[x.qoff + j];
+                if (pg->n_roots) pg->n_roots[c.pos] = x.n_roots;
+                if (pg->n_caused) pg->n_caused[c.pos] = o.x;
+                if (pg->stake) pg->stake[c.pos] = o.y;
+                if (pg->root_stake) pg->root_stake[c.pos] = ((uint64_t)o.w << 32) | o.z;
+                if (pg->pairs) {
+                    const uint32_t *src = a->pp_pin + x.pair0 + (uint64_t)j * x.n_roots;
+                    a->pp_ent[c.pos] = lx_abft::PairEnt{a->pp_keep.size(), x.n_roots, x.frame};
+                    a->pp_keep.insert(a->pp_keep.end(), src, src + x.n_roots);
+                }
             }
+        }
     }
+    return 0;
+}
+
+int build_frames(lx_abft *a, uint32_t n, const uint32_t *creator, const uint32_t *seq, const uint64_t *poff,
+                 const uint32_t *par, uint32_t *out_frame, uint8_t *out_is_root, uint32_t *err_index,
+                 const Progress *pg = nullptr) {
+    IndexView iv;
+    int rc = lx_index_peek(a->ix, &iv);
+    if (rc) return a->ixfail(rc);
+    IndexHostMeta hm;
+    if ((rc = lx_index_host_meta(a->ix, &hm))) return a->ixfail(rc);
+    const uint64_t n_ev = std::min<uint64_t>(iv.n_events, a->ev_frame.size());
+    // ---- input checks (host tables only)
+    BuildTables t;
+    ARC(build_tables(a, hm, n_ev, n, creator, seq, poff, par, pg, err_index, &t));
+    for (uint32_t i = 0; i < n; i++) {
+        out_frame[i] = 1;
+        if (out_is_root) out_is_root[i] = 1;
+    }
+    if (pg) {
+        if (pg->n_roots) std::fill(pg->n_roots, pg->n_roots + n, 0u);
+        if (pg->n_caused) std::fill(pg->n_caused, pg->n_caused + n, 0u);
+        if (pg->stake) std::fill(pg->stake, pg->stake + n, 0u);
+        if (pg->root_stake) std::fill(pg->root_stake, pg->root_stake + n, (uint64_t)0);
+        if (pg->pairs) a->pp_ent.assign(n, lx_abft::PairEnt{0, 0, 0});
+    }
+    if (t.act.empty()) return 0;
+
+    // ---- the virtual rows
+    if ((rc = lx_index_view(a->ix, &iv))) return a->ixfail(rc);   // the pending small-batch run is in the planes
+    if (iv.shard_count > 1 || iv.loading) return a->fail(LX_ERR_STATE, "abft needs an unsharded, loaded index");
+    const uint64_t up0 = a->up.launches;
+    BuildSteps own{};
+    BuildRowsArgs ra;
+    ARC(build_plane(a, iv, t, &own, &ra));
+
+    // ---- the frame loop, one wait per round
+    ARC(build_rounds(a, iv, t.act, own, pg));
     a->bstats.launches += (uint32_t)(a->up.launches - up0);
-    for (const BuildCand &c : act) {
+    for (const BuildCand &c : t.act) {
         out_frame[c.pos] = c.f;
         if (out_is_root) out_is_root[c.pos] = c.f != c.spf;
     }
+    return 0;
+}
+
+// lx_abft_event_progress: indexed events at their own frame (or the frame
+// asked), one step per frame, one round; the plain root-FC kernels on the
+// index's HB plane.
+int event_progress(lx_abft *a, uint32_t n, const uint32_t *ev, uint32_t *out_frame, uint32_t *err_index,
+                   const Progress *pg) {
+    IndexView iv;
+    int rc = lx_index_peek(a->ix, &iv);
+    if (rc) return a->ixfail(rc);
+    const uint64_t n_ev = std::min<uint64_t>(iv.n_events, a->ev_frame.size());
+    std::vector<BuildCand> act(n);
+    for (uint32_t i = 0; i < n; i++) {
+        const uint32_t at = pg->at_frame ? pg->at_frame[i] : LX_FRAME_BUILD;
+        if (ev[i] >= n_ev || at == 0) {
+            if (err_index) *err_index = i;
+            return a->fail(LX_ERR_ARG, "entry %u: %s", i, at == 0 ? "at_frame 0" : "event out of range");
+        }
+        const uint32_t f = at == LX_FRAME_BUILD ? a->ev_frame[ev[i]] : at;
+        act[i] = BuildCand{i, f, f, true};
+    }
+    if (pg->n_roots) std::fill(pg->n_roots, pg->n_roots + n, 0u);
+    if (pg->n_caused) std::fill(pg->n_caused, pg->n_caused + n, 0u);
+    if (pg->stake) std::fill(pg->stake, pg->stake + n, 0u);
+    if (pg->root_stake) std::fill(pg->root_stake, pg->root_stake + n, (uint64_t)0);
+    if (pg->pairs) a->pp_ent.assign(n, lx_abft::PairEnt{0, 0, 0});
+    for (uint32_t i = 0; i < n; i++) out_frame[i] = act[i].f;
+    if ((rc = lx_index_view(a->ix, &iv))) return a->ixfail(rc);   // the pending small-batch run is in the planes
+    if (iv.shard_count > 1 || iv.loading) return a->fail(LX_ERR_STATE, "abft needs an unsharded, loaded index");
+    const uint64_t up0 = a->up.launches;
+    BuildSteps own{};
+    own.seq16 = true;
+    ARC(build_rounds(a, iv, act, own, pg));
+    a->bstats.launches += (uint32_t)(a->up.launches - up0);
     return 0;
 }
 
@@ -1989,6 +2199,7 @@ void lx_abft_destroy(lx_abft *a) {
     a->ea_args.release();
     a->d_fcargs.release();
     a->d_qargs.release();
+    a->d_pgargs.release();
     a->b_plane.release();
     a->b_tab.release();
     a->b_bits.release();
@@ -1998,6 +2209,8 @@ void lx_abft_destroy(lx_abft *a) {
     a->up.release();
     if (a->q_pin) (void)hipHostFree(a->q_pin);
     if (a->rb_pin) (void)hipHostFree(a->rb_pin);
+    if (a->pg_pin) (void)hipHostFree(a->pg_pin);
+    if (a->pp_pin) (void)hipHostFree(a->pp_pin);
     for (hipEvent_t e : a->fc_ev) (void)hipEventDestroy(e);
     a->pool.drain();
     delete a;
@@ -2008,6 +2221,7 @@ const char *lx_abft_last_error(const lx_abft *a) { return a ? a->err.c_str() : "
 int lx_abft_bootstrap(lx_abft *a, uint32_t epoch, uint32_t nv, const uint32_t *w, const lx_abft_callbacks *cb) {
     if (!a) return LX_ERR_ARG;
     if (a->booted) return a->fail(LX_ERR_STATE, "already bootstrapped");
+    clear_pairs(a);
     a->cb = cb ? *cb : lx_abft_callbacks{};
     ARC(start_epoch(a, epoch, nv, w));
     a->booted = true;
@@ -2020,6 +2234,7 @@ int lx_abft_restore(lx_abft *a, uint32_t epoch, uint32_t nv, const uint32_t *w, 
                     const uint32_t *root_ev, const lx_abft_callbacks *cb) {
     if (!a) return LX_ERR_ARG;
     if (a->booted) return a->fail(LX_ERR_STATE, "already bootstrapped");
+    clear_pairs(a);
     IndexView iv;
     int rc = lx_index_view(a->ix, &iv);   // refuses an index without an epoch
     if (rc) return a->ixfail(rc);
@@ -2099,6 +2314,7 @@ int lx_abft_set_option(lx_abft *a, const char *name, int64_t value) {
 int lx_abft_reset(lx_abft *a, uint32_t epoch, uint32_t nv, const uint32_t *w) {
     if (!a) return LX_ERR_ARG;
     if (!a->booted) return a->fail(LX_ERR_STATE, "not bootstrapped");
+    clear_pairs(a);
     return start_epoch(a, epoch, nv, w);
 }
 
@@ -2109,6 +2325,7 @@ int lx_abft_process_batch(lx_abft *a, uint32_t n, const uint32_t *creator, const
     if (!a->booted) return a->fail(LX_ERR_STATE, "not bootstrapped");
     a->stats = lx_abft_stats{};
     a->blog.clear();
+    clear_pairs(a);
     return process(a, n, creator, seq, poff, par, claimed, out_frame, consumed);
 }
 
@@ -2132,6 +2349,7 @@ int lx_abft_build(lx_abft *a, uint32_t creator, uint32_t seq, uint32_t np, const
     if (!a || !out_frame) return LX_ERR_ARG;
     if (!a->booted) return a->fail(LX_ERR_STATE, "not bootstrapped");
     const uint64_t base = a->ev_frame.size();
+    clear_pairs(a);
     Snapshot snap = take_snapshot(a);
     uint64_t poff[2] = {0, np};
     int rc = add_events(a, 1, &creator, &seq, poff, parents);
@@ -2148,6 +2366,7 @@ int lx_abft_build_frames(lx_abft *a, uint32_t n, const uint32_t *creator, const 
                          const uint32_t *par, uint32_t *out_frame, uint8_t *out_is_root, uint32_t *err_index) {
     if (!a) return LX_ERR_ARG;
     a->bstats = lx_abft_build_stats{};
+    clear_pairs(a);
     if (err_index) *err_index = 0;
     if (!a->booted) return a->fail(LX_ERR_STATE, "not bootstrapped");
     if (!n) return 0;
@@ -2155,6 +2374,62 @@ int lx_abft_build_frames(lx_abft *a, uint32_t n, const uint32_t *creator, const 
     const int rc = build_frames(a, n, creator, seq, poff, par, out_frame, out_is_root, err_index);
     if (rc == LX_ERR_ARG) a->bstats = lx_abft_build_stats{};
     return rc;
+}
+
+int lx_abft_build_progress(lx_abft *a, uint32_t n, const uint32_t *creator, const uint32_t *seq, const uint64_t *poff,
+                           const uint32_t *par, const uint32_t *at_frame, uint32_t flags, uint32_t *out_frame,
+                           uint32_t *out_n_roots, uint32_t *out_n_caused, uint32_t *out_stake,
+                           uint64_t *out_root_stake, uint32_t *err_index) {
+    if (!a) return LX_ERR_ARG;
+    a->bstats = lx_abft_build_stats{};
+    clear_pairs(a);
+    if (err_index) *err_index = 0;
+    if (!a->booted) return a->fail(LX_ERR_STATE, "not bootstrapped");
+    if (flags & ~LX_PROGRESS_PAIRS) return a->fail(LX_ERR_ARG, "unknown flags");
+    if (!n) return 0;
+    if (!creator || !seq || !poff || !out_frame) return a->fail(LX_ERR_ARG, "null input");
+    const Progress pg{nullptr, at_frame, (flags & LX_PROGRESS_PAIRS) != 0, out_n_roots, out_n_caused, out_stake,
+                      out_root_stake};
+    const int rc = build_frames(a, n, creator, seq, poff, par, out_frame, nullptr, err_index, &pg);
+    if (rc == LX_ERR_ARG) a->bstats = lx_abft_build_stats{};
+    if (rc) clear_pairs(a);
+    return rc;
+}
+
+int lx_abft_event_progress(lx_abft *a, uint32_t n, const uint32_t *ev, const uint32_t *at_frame, uint32_t flags,
+                           uint32_t *out_frame, uint32_t *out_n_roots, uint32_t *out_n_caused, uint32_t *out_stake,
+                           uint64_t *out_root_stake, uint32_t *err_index) {
+    if (!a) return LX_ERR_ARG;
+    a->bstats = lx_abft_build_stats{};
+    clear_pairs(a);
+    if (err_index) *err_index = 0;
+    if (!a->booted) return a->fail(LX_ERR_STATE, "not bootstrapped");
+    if (flags & ~LX_PROGRESS_PAIRS) return a->fail(LX_ERR_ARG, "unknown flags");
+    if (!n) return 0;
+    if (!ev || !out_frame) return a->fail(LX_ERR_ARG, "null input");
+    const Progress pg{ev, at_frame, (flags & LX_PROGRESS_PAIRS) != 0, out_n_roots, out_n_caused, out_stake,
+                      out_root_stake};
+    const int rc = event_progress(a, n, ev, out_frame, err_index, &pg);
+    if (rc == LX_ERR_ARG) a->bstats = lx_abft_build_stats{};
+    if (rc) clear_pairs(a);
+    return rc;
+}
+
+int lx_abft_last_progress_pairs(lx_abft *a, uint64_t *pair_off, uint32_t *out_root, uint32_t *out_stake, uint64_t cap,
+                                uint64_t *n_pairs) {
+    if (!a || !n_pairs) return LX_ERR_ARG;
+    uint64_t total = 0;
+    for (size_t i = 0; i < a->pp_ent.size(); i++) {
+        const lx_abft::PairEnt &e = a->pp_ent[i];
+        if (pair_off) pair_off[i] = total;
+        const uint64_t w = total < cap ? std::min<uint64_t>(e.n, cap - total) : 0;
+        if (w && out_root) std::copy_n(a->frames[e.frame].ev.begin(), w, out_root + total);
+        if (w && out_stake) std::copy_n(a->pp_keep.begin() + e.off, w, out_stake + total);
+        total += e.n;
+    }
+    if (pair_off) pair_off[a->pp_ent.size()] = total;
+    *n_pairs = total;
+    return 0;
 }
 
 int lx_abft_build_last_stats(const lx_abft *a, lx_abft_build_stats *out) {

@@ -512,6 +512,87 @@ hipError_t launch_root_quorum_multi(const QuorumArgs *am, uint32_t n_steps, uint
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------- k_root_progress
+// The read-out of a frame step (lx_abft_build_progress, lx_abft_event_progress;
+// DESIGN.md section 9d): one wave per candidate, as k_root_quorum, but the
+// stake sums are kept instead of reduced to bits.  stake(e, r) = the sum over
+// the column splits, 0 under the early-false flag (bit 31).  Per candidate,
+// its own root slot left out: the slots with stake >= quorum (n_caused), the
+// stake of their distinct creators (dup chain over the bit row in LDS),
+// sum of min(stake, quorum) (root_stake), and the quorum byte the frame loop
+// reads.  The bit row stays in LDS: nobody reads these steps' rows later.
+// pairs (optional): stake(e, r) per slot, own slot included.
+template <bool MULTI>
+__global__ __launch_bounds__(256) void k_root_progress(ProgressArgs a1, const ProgressArgs *am, uint32_t n_steps) {
+    __shared__ uint32_t sRow[4][kRowWords];
+    const ProgressArgs a = MULTI ? am[step_of(am, n_steps, blockIdx.x)] : a1;
+    const uint32_t wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const uint32_t wave = (blockIdx.x - (MULTI ? a.block0 : 0u)) * 4 + wv;
+    if (wave >= a.n_cand) return;
+    const uint32_t rp = a.words * 32;
+    const uint32_t self = a.cand[wave];
+    uint32_t caused = 0;
+    unsigned long long rs = 0;   // at most 16384 slots x quorum < 2^45
+    for (uint32_t r0 = 0; r0 < rp; r0 += 64) {
+        const uint32_t r = r0 + lane;
+        uint32_t sum = 0;
+        for (uint32_t z = 0; z < a.n_split; z++) sum += a.psum[((uint64_t)z * a.n_cand + wave) * rp + r];
+        const uint32_t rev = r < a.n_roots ? a.root_ev[r] : LX_NONE;
+        const uint32_t st = (rev != LX_NONE && !(sum >> 31)) ? sum : 0u;
+        const bool ok = st >= a.quorum;   // quorum >= 1
+        const unsigned long long m = __ballot(ok);
+        if (lane < 2 && r0 / 32 + lane < a.words) sRow[wv][r0 / 32 + lane] = (uint32_t)(m >> (32 * lane));
+        if (a.pairs && r < a.n_roots) a.pairs[(uint64_t)wave * a.n_roots + r] = st;
+        if (rev != LX_NONE && rev != self) {
+            caused += ok ? 1u : 0u;
+            rs += st < a.quorum ? st : a.quorum;
+        }
+    }
+    __syncthreads();   // sRow of this wave complete (waves of a block exit together below)
+    uint32_t sum = 0;
+    for (uint32_t wi = lane; wi < a.words; wi += 64) {
+        uint32_t m = sRow[wv][wi];
+        while (m) {
+            const uint32_t b = __builtin_ctz(m);
+            m &= m - 1;
+            const uint32_t r = wi * 32 + b;
+            if (a.root_ev[r] == self) continue;   // as k_root_quorum: never its own slot
+            bool first = true;
+            for (uint32_t d = a.dup[r]; d != LX_NONE; d = a.dup[d])
+                if (a.root_ev[d] != self && ((sRow[wv][d >> 5] >> (d & 31)) & 1u)) { first = false; break; }
+            if (first) sum += a.wcreator[a.creator[r]];
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        sum += __shfl_xor(sum, off, 64);
+        caused += __shfl_xor(caused, off, 64);
+        const uint32_t lo = __shfl_xor((uint32_t)rs, off, 64), hi = __shfl_xor((uint32_t)(rs >> 32), off, 64);
+        rs += ((unsigned long long)hi << 32) | lo;
+    }
+    if (lane == 0) {
+        a.q[wave] = sum >= a.quorum ? 1 : 0;
+        uint4 o;
+        o.x = caused;
+        o.y = sum;
+        o.z = (uint32_t)rs;
+        o.w = (uint32_t)(rs >> 32);
+        a.out[wave] = o;
+    }
+}
+
+hipError_t launch_root_progress(const ProgressArgs &a, hipStream_t s) {
+    if (!a.n_cand) return hipSuccess;
+    hipLaunchKernelGGL(k_root_progress<false>, dim3((a.n_cand + 3) / 4), dim3(256), 0, s, a, nullptr, 0);
+    return hipGetLastError();
+}
+
+hipError_t launch_root_progress_multi(const ProgressArgs *am, uint32_t n_steps, uint32_t blocks, hipStream_t s) {
+    if (!n_steps || !blocks) return hipSuccess;
+    hipLaunchKernelGGL(k_root_progress<true>, dim3(blocks), dim3(256), 0, s, ProgressArgs{}, am, n_steps);
+    return hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------- k_fc_tile_out
 // ForklessCause answers of a whole k_root_fc launch as bytes (the per-pair
 // result cache, lx_fccache.cpp): out[c * pitch + r] = tag[r] << 1 | FC(cand c,

@@ -725,6 +725,26 @@ struct QuorumArgs {
     uint32_t block0;             // merged launch: this step's first workgroup
 };
 
+// k_root_progress: the stake sums behind one candidate's frame step (lx_abft_build_progress,
+// lx_abft_event_progress).  The fields of QuorumArgs without the bit rows, plus the read-out.
+struct ProgressArgs {
+    const uint32_t *psum;        // partial stake sums of k_root_fc (bit 31 of split 0: early false)
+    uint32_t n_split;
+    uint32_t words;              // psum row pitch / 32
+    uint32_t n_roots;
+    uint32_t n_cand;
+    const uint32_t *cand;        // candidate events (their own slot is left out of the sums); NONE: none
+    const uint32_t *root_ev;     // root events of the frame
+    const uint32_t *creator;     // creator idx per root
+    const uint32_t *dup;         // previous root of the same creator, or NONE
+    const uint32_t *wcreator;    // weight by creator idx
+    uint32_t quorum;
+    uint8_t *q;                  // out: stake >= quorum
+    uint4 *out;                  // out [n_cand]: n_caused, stake, root_stake (low, high)
+    uint32_t *pairs;             // out [n_cand][n_roots]: stake(e, r), own slot included; NULL: not asked
+    uint32_t block0;             // merged launch: this step's first workgroup
+};
+
 struct BuildRowsArgs {
     const uint32_t *hb;
     uint64_t stride;
@@ -946,6 +966,8 @@ hipError_t launch_root_fc_own_multi(const RootFcArgs *am, uint32_t n_steps, uint
 hipError_t launch_build_rows(const BuildRowsArgs &a, bool forks, hipStream_t s);   // lx_abft_build.hip
 hipError_t launch_root_quorum_multi(const QuorumArgs *am, uint32_t n_steps, uint32_t blocks, hipStream_t s);
 hipError_t launch_root_quorum(const QuorumArgs &a, hipStream_t s);
+hipError_t launch_root_progress_multi(const ProgressArgs *am, uint32_t n_steps, uint32_t blocks, hipStream_t s);
+hipError_t launch_root_progress(const ProgressArgs &a, hipStream_t s);
 hipError_t launch_fc_tile_out(const uint32_t *psum, uint32_t n_split, uint32_t n_cand, uint32_t rp, uint32_t n_roots,
                               uint32_t quorum, const uint8_t *tag, uint8_t *out, uint64_t pitch, hipStream_t s);
 hipError_t launch_votes(const VoteArgs &a, uint32_t n_voters, bool round1, hipStream_t s);

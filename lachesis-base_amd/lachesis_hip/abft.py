@@ -15,6 +15,9 @@ abft/common_test.go drives FakeLachesis:
 * ``build_frames(events)``                 -- Build for candidate events that are
   not added (lx_abft_build_frames): sets ``e.frame``, returns the is-root
   flags; no Add, no rollback
+* ``build_progress(events)`` / ``event_progress(events)`` -- how far candidate
+  or processed events are from the next frame (lx_abft_build_progress,
+  lx_abft_event_progress); ``progress_pairs()`` reads the per-root stakes
 * ``reset(epoch, validators)``             -- Orderer.Reset (abft/bootstrap.go:54-65)
 * ``state()`` / ``restore(state, index_db, get_event, begin_block)`` -- the
   abft state a caller persists, and Bootstrap over it after a restart
@@ -116,6 +119,79 @@ def build_frames_arrays(L, h, creator, seq, poff, par, chk=None):
         ex.err_index = err.value
         raise ex
     return frames[:n], roots[:n]
+
+
+PROGRESS_PAIRS = 1
+PROGRESS_FIELDS = ("frame", "n_roots", "n_caused", "stake", "root_stake")
+
+
+def _progress_out(n):
+    out = {f: np.zeros(max(n, 1), dtype=np.uint64 if f == "root_stake" else np.uint32) for f in PROGRESS_FIELDS}
+    ptrs = [_p(out[f], u64p if f == "root_stake" else u32p) for f in PROGRESS_FIELDS]
+    return out, ptrs
+
+
+def _progress_done(L, h, rc, err, out, n, chk):
+    res = {f: v[:n] for f, v in out.items()}
+    if chk is None:
+        return rc, err.value, res
+    if rc != 0:
+        ex = LxError(rc, L.lx_abft_last_error(h).decode())
+        ex.err_index = err.value
+        raise ex
+    return res
+
+
+def build_progress_arrays(L, h, creator, seq, poff, par, at_frame=None, pairs=False, chk=None, flags=None):
+    """lx_abft_build_progress on dense arrays: a dict of arrays ``frame``,
+    ``n_roots``, ``n_caused``, ``stake``, ``root_stake`` per candidate.
+    ``at_frame``: per candidate FRAME_BUILD or the frame to ask (None: Build
+    frames).  ``pairs`` keeps the pair stakes for :func:`progress_pairs`.
+    Without ``chk`` returns (rc, err_index, dict) instead of raising."""
+    creator = np.ascontiguousarray(creator, dtype=np.uint32)
+    seq = np.ascontiguousarray(seq, dtype=np.uint32)
+    poff = np.ascontiguousarray(poff, dtype=np.uint64)
+    par = np.ascontiguousarray(par if len(par) else [0], dtype=np.uint32)
+    n = len(creator)
+    at = None if at_frame is None else np.ascontiguousarray(at_frame if n else [0], dtype=np.uint32)
+    out, ptrs = _progress_out(n)
+    err = ctypes.c_uint32()
+    fl = (PROGRESS_PAIRS if pairs else 0) if flags is None else int(flags)
+    rc = L.lx_abft_build_progress(h, n, _p(creator, u32p), _p(seq, u32p), _p(poff, u64p), _p(par, u32p),
+                                  None if at is None else _p(at, u32p), fl, *ptrs, ctypes.byref(err))
+    return _progress_done(L, h, rc, err, out, n, chk)
+
+
+def event_progress_arrays(L, h, events, at_frame=None, pairs=False, chk=None, flags=None):
+    """lx_abft_event_progress: the same for indexed events (dense indices)."""
+    n = len(events)
+    ev = np.ascontiguousarray(events if n else [0], dtype=np.uint32)
+    at = None if at_frame is None else np.ascontiguousarray(at_frame if n else [0], dtype=np.uint32)
+    out, ptrs = _progress_out(n)
+    err = ctypes.c_uint32()
+    fl = (PROGRESS_PAIRS if pairs else 0) if flags is None else int(flags)
+    rc = L.lx_abft_event_progress(h, n, _p(ev, u32p), None if at is None else _p(at, u32p), fl, *ptrs,
+                                  ctypes.byref(err))
+    return _progress_done(L, h, rc, err, out, n, chk)
+
+
+def progress_pairs(L, h, n, cap=None):
+    """lx_abft_last_progress_pairs after a progress call of ``n`` entries made
+    with ``pairs``: (pair_off[n + 1], root events, stakes, n_pairs).  ``cap``
+    limits the entries written (None: all); n_pairs is the full count.  After
+    any other call on the handle the reader is empty: pass n = 0."""
+    total = ctypes.c_uint64()
+    off = np.zeros(n + 1, dtype=np.uint64)
+    rc = L.lx_abft_last_progress_pairs(h, _p(off, u64p), None, None, 0, ctypes.byref(total))
+    if rc != 0:
+        raise LxError(rc, L.lx_abft_last_error(h).decode())
+    want = total.value if cap is None else min(int(cap), total.value)
+    root = np.zeros(max(want, 1), dtype=np.uint32)
+    stake = np.zeros(max(want, 1), dtype=np.uint32)
+    rc = L.lx_abft_last_progress_pairs(h, _p(off, u64p), _p(root, u32p), _p(stake, u32p), want, ctypes.byref(total))
+    if rc != 0:
+        raise LxError(rc, L.lx_abft_last_error(h).decode())
+    return off, root[:want], stake[:want], total.value
 
 
 class AbftState(ctypes.Structure):
@@ -343,8 +419,35 @@ class IndexedLachesis:
             e.frame = int(f)
         return [bool(r) for r in roots]
 
+    def build_progress(self, events, at_frame=None, pairs=False):
+        """Frame progress of candidate events that are not added
+        (lx_abft_build_progress): a dict of arrays ``frame``, ``n_roots``,
+        ``n_caused``, ``stake``, ``root_stake`` per candidate -- how far each
+        is from the next frame.  Nothing is added or rolled back."""
+        creator = np.array([self.validators.idxs[e.creator] for e in events], dtype=np.uint32)
+        seq = np.array([e.seq for e in events], dtype=np.uint32)
+        off = np.zeros(len(events) + 1, dtype=np.uint64)
+        flat = []
+        for k, e in enumerate(events):
+            flat.extend(self.pos[p] for p in e.parents)
+            off[k + 1] = len(flat)
+        self._progress_n = len(events)
+        return build_progress_arrays(self.L, self.h, creator, seq, off, flat, at_frame, pairs, self._chk)
+
+    def event_progress(self, events, at_frame=None, pairs=False):
+        """The same for events already processed (lx_abft_event_progress)."""
+        self._progress_n = len(events)
+        return event_progress_arrays(self.L, self.h, [self.pos[e.id] for e in events], at_frame, pairs, self._chk)
+
+    def progress_pairs(self, cap=None):
+        """Pair stakes of the last progress call made with ``pairs``:
+        (pair_off, root event ids, stakes, n_pairs)."""
+        off, root, stake, total = progress_pairs(self.L, self.h, getattr(self, "_progress_n", 0), cap)
+        return off, [self.evs[r].id for r in root], stake, total
+
     def build_stats(self):
-        """lx_abft_build_last_stats: GPU work of the last :meth:`build_frames`."""
+        """lx_abft_build_last_stats: GPU work of the last :meth:`build_frames`
+        or progress call."""
         st = BuildStats()
         self._chk(self.L.lx_abft_build_last_stats(self.h, ctypes.byref(st)))
         return {f: getattr(st, f) for f, _ in BuildStats._fields_}
@@ -562,6 +665,21 @@ class DenseLachesis:
         """lx_abft_build_frames: (rc, err_index, frames, is_root) of candidate
         events that are not added."""
         return build_frames_arrays(self.L, self.h, creator, seq, poff, par)
+
+    def build_progress(self, creator, seq, poff, par, at_frame=None, pairs=False, flags=None):
+        """lx_abft_build_progress: (rc, err_index, dict of arrays ``frame``,
+        ``n_roots``, ``n_caused``, ``stake``, ``root_stake``) of candidate
+        events that are not added."""
+        return build_progress_arrays(self.L, self.h, creator, seq, poff, par, at_frame, pairs, flags=flags)
+
+    def event_progress(self, events, at_frame=None, pairs=False, flags=None):
+        """lx_abft_event_progress: the same for indexed events."""
+        return event_progress_arrays(self.L, self.h, events, at_frame, pairs, flags=flags)
+
+    def progress_pairs(self, n, cap=None):
+        """lx_abft_last_progress_pairs after a progress call of n entries:
+        (pair_off, root events, stakes, n_pairs)."""
+        return progress_pairs(self.L, self.h, n, cap)
 
     def build_stats(self):
         """lx_abft_build_last_stats."""

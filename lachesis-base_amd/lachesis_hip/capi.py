@@ -126,6 +126,11 @@ SIGNATURES = [
     ("lx_abft_build_frames", ctypes.c_int, [vp, ctypes.c_uint32, u32p, u32p, u64p, u32p, u32p,
                                             ctypes.POINTER(ctypes.c_uint8), u32p]),
     ("lx_abft_build_last_stats", ctypes.c_int, [vp, vp]),
+    ("lx_abft_build_progress", ctypes.c_int, [vp, ctypes.c_uint32, u32p, u32p, u64p, u32p, u32p, ctypes.c_uint32,
+                                              u32p, u32p, u32p, u32p, u64p, u32p]),
+    ("lx_abft_event_progress", ctypes.c_int, [vp, ctypes.c_uint32, u32p, u32p, ctypes.c_uint32,
+                                              u32p, u32p, u32p, u32p, u64p, u32p]),
+    ("lx_abft_last_progress_pairs", ctypes.c_int, [vp, u64p, u32p, u32p, ctypes.c_uint64, u64p]),
     ("lx_abft_epoch", ctypes.c_uint32, [vp]),
     ("lx_abft_last_decided_frame", ctypes.c_uint32, [vp]),
     ("lx_abft_frame_roots", ctypes.c_int, [vp, ctypes.c_uint32, u32p, ctypes.c_uint32, u32p]),
