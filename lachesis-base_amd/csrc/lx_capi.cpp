@@ -3371,7 +3371,7 @@ int lx_load_finish(lx_index *h, const uint8_t *bi_rlp, uint32_t bi_len) {
 
 }  // extern "C"
 
-// view for the abft engine (lx_abft.cpp); see lx_internal.h
+// view for the abft engine (lx_abft_engine.h); see lx_internal.h
 int lx_index_view(lx_index *h, IndexView *o) {
     if (!h || !o) return LX_ERR_ARG;
     WHOLE_INDEX(h);

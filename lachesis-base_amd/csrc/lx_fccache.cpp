@@ -273,34 +273,24 @@ int fcc_tile(lx_index *h, FcCache *c) {
     if ((rc = fcc_cheaters(h, c))) return rc;
     const uint32_t n = c->used, words = (n + 31) / 32, rp = words * 32;
     const uint32_t ncols = (h->V + 31) / 32 * 32;
-    const uint32_t splits = lx::root_fc_splits(n, n, ncols);
-    const uint32_t col_split = ((ncols + splits - 1) / splits + 31) / 32 * 32;
-    const uint32_t n_split = (ncols + col_split - 1) / col_split;
-    const uint64_t need = (uint64_t)n_split * n * rp;
+    const FcColSplit sp = fc_col_split(fc_tiles(n, n), ncols);
+    const uint64_t need = (uint64_t)sp.n_split * n * rp;
     if (need > c->d_psum.cap()) HIPCHK(h, c->d_psum.renew(need, h->stream, true));
-    RootFcArgs r{};
-    r.hb = h->lay.hb;
-    r.la = h->lay.la;
-    r.stride = h->pstride;
-    r.cand = c->evk_d;
-    r.n_cand = n;
-    r.roots = c->evk_d;
-    r.n_roots = n;
-    r.roots_fallback = c->evk[0];
-    r.ncols = ncols;
-    r.wpad = h->lay.wpad;
-    r.quorum = h->quorum;
-    r.n_k = c->n_k;
-    r.kcol = c->d_k;
-    r.kflag = c->d_k + c->n_k;
-    r.kw = c->d_k + 2ull * c->n_k;
-    r.ev_branch = h->lay.ev_branch;
-    r.psum = c->d_psum;
-    r.words = words;
-    r.col_split = col_split;
-    r.n_split = n_split;
+    RootFcArgs base{};
+    base.hb = h->lay.hb;
+    base.la = h->lay.la;
+    base.stride = h->pstride;
+    base.ncols = ncols;
+    base.wpad = h->lay.wpad;
+    base.quorum = h->quorum;
+    base.n_k = c->n_k;
+    base.kcol = c->d_k;
+    base.kflag = c->d_k + c->n_k;
+    base.kw = c->d_k + 2ull * c->n_k;
+    base.ev_branch = h->lay.ev_branch;
+    const RootFcArgs r = lx::root_fc_step(base, c->evk_d, n, c->evk_d, n, c->evk[0], c->d_psum, words, sp);
     HIPCHK(h, lx::launch_root_fc(r, h->B > h->V, h->pack16 && h->max_seq <= 0xFFFFu, h->stream));
-    HIPCHK(h, lx::launch_fc_tile_out(c->d_psum, n_split, n, rp, n, h->quorum, c->g7_d, c->M_dev, c->W, h->stream));
+    HIPCHK(h, lx::launch_fc_tile_out(c->d_psum, sp.n_split, n, rp, n, h->quorum, c->g7_d, c->M_dev, c->W, h->stream));
     c->st.tile_fills++;
     c->st.pairs += (uint64_t)n * n;
     return 0;

@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "lx_fc_split.h"
 #include "lx_walk_plan.h"
 
 #define LX_NONE 0xFFFFFFFFu
@@ -667,7 +668,7 @@ struct AncForkListArgs {
     uint32_t *n_found;           // [n_heads]
 };
 
-// ---- batched abft caller (lx_abft_kernels.hip, lx_abft.cpp)
+// ---- batched abft caller (lx_abft_kernels.hip, lx_abft_engine.h)
 // lx_abft_build_frames: n candidate events that are not added.  Candidate c is
 // row c of a scratch plane (k_build_rows, lx_abft_build.hip); the OWN forms of
 // the root-FC kernels read the per-candidate tables for the own-creator term.
@@ -957,6 +958,24 @@ hipError_t launch_anc_fork(const AncForkArgs &a, hipStream_t s);
 // flags, scan and compaction of one grid launch into the ordered list
 hipError_t launch_anc_fork_list(const AncForkListArgs &a, void *tmp, size_t tmp_bytes, hipStream_t s);
 uint32_t root_fc_splits(uint32_t n_cand, uint32_t n_roots, uint32_t ncols);
+// One step's RootFcArgs: `base` holds what every step on the index shares (the
+// planes, weights and quorum, the cheaters' columns, the OWN tables); block0 is
+// the caller's.
+inline RootFcArgs root_fc_step(const RootFcArgs &base, const uint32_t *cand, uint32_t n_cand, const uint32_t *roots,
+                               uint32_t n_roots, uint32_t roots_fallback, uint32_t *psum, uint32_t words,
+                               FcColSplit sp) {
+    RootFcArgs r = base;
+    r.cand = cand;
+    r.n_cand = n_cand;
+    r.roots = roots;
+    r.n_roots = n_roots;
+    r.roots_fallback = roots_fallback;
+    r.psum = psum;
+    r.words = words;
+    r.col_split = sp.col_split;
+    r.n_split = sp.n_split;
+    return r;
+}
 hipError_t launch_root_fc(const RootFcArgs &a, bool forks, bool seq16, hipStream_t s);
 uint32_t root_fc_blocks(const RootFcArgs &a);
 hipError_t launch_root_fc_multi(const RootFcArgs *am, uint32_t n_steps, uint32_t blocks, bool forks, bool seq16,

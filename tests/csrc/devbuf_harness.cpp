@@ -4,7 +4,9 @@
 //
 // The backend counts live blocks and its own calls (allocations, fills, copies
 // and waits, in the order they are made) and fails the k-th of them when told
-// to.  -DDEVBUF_MAIN adds a main() that walks the same properties the Python
+// to.  The pooled buffer (BlockPool, PoolBuf) runs over the same backend, with
+// byte elements so that the sizes of the test are the sizes of the blocks.
+// -DDEVBUF_MAIN adds a main() that walks the same properties the Python
 // test asserts: a stand-alone program for a run under the host sanitizers
 // (g++ -fsanitize=address,undefined -DDEVBUF_MAIN).
 #include <cstdio>
@@ -55,6 +57,13 @@ struct Several {
     lxi::DevBuf<uint8_t, HostMem> bytes;
 };
 
+using Pool = lxi::BlockPool<HostMem>;
+using PBuf = lxi::PoolBuf<uint8_t, HostMem>;
+struct SeveralPooled {
+    PBuf a, b;
+    lxi::PoolBuf<uint32_t, HostMem> words;
+};
+
 }  // namespace
 
 extern "C" {
@@ -86,6 +95,38 @@ long db_several(uint64_t n) {
     if (s.a.renew(n) || s.b.grow(2 * n) || s.c.regrow(n, 0, lxi::Fill::all, 0) || s.bytes.renew(3)) return -1;
     Several t = std::move(s);
     return HostMem::live;
+}
+
+// ---- the pooled buffer
+void *pl_new() { return new Pool(); }
+void pl_delete(void *p) { delete static_cast<Pool *>(p); }
+void pl_drain(void *p) { static_cast<Pool *>(p)->drain(); }
+long pl_idle(void *p) { return (long)static_cast<Pool *>(p)->idle(); }
+void *pb_new() { return new PBuf(); }
+void pb_delete(void *b) { delete static_cast<PBuf *>(b); }
+const void *pb_ptr(void *b) { return static_cast<PBuf *>(b)->get(); }
+uint64_t pb_cap(void *b) { return static_cast<PBuf *>(b)->cap(); }
+int pb_regrow(void *b, void *pool, uint64_t n, uint64_t keep) {
+    return static_cast<PBuf *>(b)->regrow(*static_cast<Pool *>(pool), n, keep, 0);
+}
+void pb_release(void *b) { static_cast<PBuf *>(b)->release(); }
+void pb_move(void *dst, void *src) { *static_cast<PBuf *>(dst) = std::move(*static_cast<PBuf *>(src)); }
+void pb_write(void *b, uint64_t i, uint8_t v) { static_cast<PBuf *>(b)->get()[i] = v; }
+uint8_t pb_read(void *b, uint64_t i) { return (*static_cast<PBuf *>(b))[i]; }
+// a struct of pooled buffers destroyed ahead of its pool, then the pool: live
+// blocks while the struct stands, once it is gone, once the pool is gone
+void pb_struct_then_pool(uint64_t n, long *standing, long *pooled, long *gone) {
+    {
+        Pool pool;
+        {
+            SeveralPooled s;
+            if (s.a.regrow(pool, n, 0, 0) || s.b.regrow(pool, 2 * n, 0, 0) || s.words.regrow(pool, n, 0, 0)) return;
+            SeveralPooled t = std::move(s);
+            *standing = HostMem::live;
+        }
+        *pooled = HostMem::live;
+    }
+    *gone = HostMem::live;
 }
 
 }  // extern "C"
@@ -133,6 +174,62 @@ int main() {
         CHECK(HostMem::live == 0 && !b.get() && b.cap() == 0);
     }
     CHECK(db_several(10) == 4 && HostMem::live == 0);
+    {
+        Pool pool;
+        PBuf b, c;
+        CHECK(b.regrow(pool, 1000, 0, 0) == 0 && b.cap() == 1000 && HostMem::live == 1);
+        const uint8_t *p = b;
+        // a released block comes back for the same size and for a smaller one, with no backend call
+        b.release();
+        CHECK(!b.get() && b.cap() == 0 && pool.idle() == 1 && HostMem::live == 1);
+        db_fail_at(0);
+        CHECK(b.regrow(pool, 1000, 0, 0) == 0 && b.get() == p && HostMem::ops == 0);
+        b.release();
+        CHECK(b.regrow(pool, 200, 0, 0) == 0 && b.get() == p && b.cap() == 1000 && HostMem::ops == 0);
+        // 400,000 > 4 * 1,000 + 65,536: refused, a fresh block instead
+        CHECK(c.regrow(pool, 400000, 0, 0) == 0);
+        c.release();
+        CHECK(c.regrow(pool, 1000, 0, 0) == 0 && c.cap() == 1000 && pool.idle() == 1 && HostMem::live == 3);
+        pool.drain();
+        CHECK(pool.idle() == 0 && HostMem::live == 2);
+        // of two free blocks the smallest sufficient one
+        b.release();
+        c.release();
+        CHECK(b.regrow(pool, 3000, 0, 0) == 0 && c.regrow(pool, 2000, 0, 0) == 0);
+        const uint8_t *p3 = b, *p2 = c;
+        b.release();
+        c.release();
+        CHECK(b.regrow(pool, 1500, 0, 0) == 0 && b.get() == p2 && b.cap() == 2000);
+        CHECK(c.regrow(pool, 2500, 0, 0) == 0 && c.get() == p3 && c.cap() == 3000);
+        // a grow that keeps a prefix: copied, the old block pooled, no wait
+        for (uint32_t i = 0; i < 2000; i++) b.get()[i] = (uint8_t)(i * 7);
+        const long syncs = HostMem::syncs, idle = (long)pool.idle();
+        CHECK(b.regrow(pool, 100000, 2000, 0) == 0 && b.get() != p2 && b.cap() == 100000);
+        CHECK(HostMem::syncs == syncs && (long)pool.idle() == idle + 1);
+        for (uint32_t i = 0; i < 2000; i++) CHECK(b[i] == (uint8_t)(i * 7));
+        // a failed allocation and a failed copy leave the buffer as it was; the
+        // block of the failed copy is the pool's, not lost
+        p = b;
+        long live = HostMem::live;
+        db_fail_at(1);
+        CHECK(b.regrow(pool, 10000000, 2000, 0) != 0 && b.get() == p && b.cap() == 100000 && HostMem::live == live);
+        db_fail_at(2);
+        CHECK(b.regrow(pool, 10000000, 2000, 0) != 0 && b.get() == p && b.cap() == 100000);
+        CHECK(HostMem::live == live + 1 && (long)pool.idle() == idle + 2);
+        db_fail_at(1);   // the block now comes from the pool: the copy is the first call
+        CHECK(b.regrow(pool, 10000000, 2000, 0) != 0 && b.get() == p && HostMem::live == live + 1);
+        CHECK((long)pool.idle() == idle + 2);
+        db_fail_at(0);
+        PBuf d = std::move(b);   // moved over: c's block goes to the pool
+        c = std::move(d);
+        CHECK(!b.get() && !d.get() && c.get() == p && (long)pool.idle() == idle + 3);
+        pool.drain();
+        CHECK(HostMem::live == 1);
+    }
+    CHECK(HostMem::live == 0);
+    long standing = -1, pooled = -1, gone = -1;
+    pb_struct_then_pool(100, &standing, &pooled, &gone);
+    CHECK(standing == 3 && pooled == 3 && gone == 0);
     printf("devbuf ok\n");
     return 0;
 }
