@@ -1,5 +1,5 @@
 """Rollback, then a fork by another creator (tests/test_refork_dags.py,
-tests/test_gpu_refork.py).
+tests/test_gpu_refork.py, tests/test_gpu_refork_readers.py).
 
 A fork gives its creator the next branch number (vecengine/index.go:105-141),
 DropNotFlushed takes it back (vecengine/index.go:88-96), and the next fork --
@@ -313,6 +313,261 @@ def get(name, abft=False):
     if key not in _cache:
         _cache[key] = found(*VARIANTS[name], abft=abft)
     return _cache[key]
+
+
+# ---------------------------------------------------------------------------- per reader
+#
+# One condition per reader of the branch tables that tests/test_gpu_refork_readers.py
+# drives: some query's right answer differs from the answer computed with the
+# fork columns of ``A`` still credited to X (``stale_map``), or with the first
+# seq X's fork branch had.  Each function returns the differing queries; an
+# empty list means that a stale table could pass in that scenario.
+
+MT_DEFAULTS = (0, 1 << 40)
+
+
+def kept(sc):
+    """The events present after drop + A2 + T, in Add order."""
+    return sc.P + sc.A2 + sc.T
+
+
+def stale_map(o, sc, bx):
+    """(creator_idxs, by_creators) of the oracle with the branch numbers ``bx``
+    credited to X, as tables built for ``A`` have them."""
+    creators = list(o.bi.creator_idxs)
+    for br in bx:
+        creators[br] = sc.X
+    by = [[] for _ in range(sc.V)]
+    for b, c in enumerate(creators):
+        by[c].append(b)
+    return creators, by
+
+
+def event_times(sc, seed):
+    """{event id: creation time} for P, A, A2 and T: mostly close together, one
+    in five far above 2^63; the events of A and of A2 at the same dense index
+    get different times."""
+    rng = SplitMix64(seed * 7919 + sc.V * 131 + sc.n)
+    out = {}
+    for e in sc.P + sc.A + sc.A2 + sc.T:
+        out[e.id] = (1 << 63) + rng.below(97) if rng.below(5) == 0 else 1000 + rng.below(400)
+    return out
+
+
+def drive_carried(sc, times):
+    """median_time_model.CarriedIndex through P, flush, A, drop, A2, T."""
+    import median_time_model as mm
+    o = mm.CarriedIndex(times)
+    o.reset(sc.validators, sc.store.get)
+    for e in sc.P:
+        o.add(e)
+    o.flush()
+    for e in sc.A:
+        o.add(e)
+    bx = [o.get_event_branch_id(f.id) for f in sc.fx]
+    o.drop_not_flushed()
+    for e in kept(sc)[len(sc.P):]:
+        o.add(e)
+    return o, bx
+
+
+def merged_times_by_map(o, eid, by_creators):
+    """CarriedIndex.merged over an explicit creator -> branches map."""
+    import median_time_model as mm
+    hb, vt = o.get_highest_before(eid), o.vtime[eid]
+    out = []
+    for branches in by_creators:
+        best, time, kind = 0, 0, mm.NONE
+        for b in branches:
+            bs = tuple(hb.get(b))
+            if bs == vo.FORK_DETECTED:
+                best, time, kind = 0, 0, mm.FORK
+                break
+            if bs[0] > best:
+                best, time, kind = bs[0], vt[b] if b < len(vt) else 0, mm.SEEN
+        out.append((kind, time))
+    return out
+
+
+def median_time_diffs(sc, times):
+    """[(head id, default, right median, stale median)] over the heads ea and
+    eb and MT_DEFAULTS where the two medians differ."""
+    import median_time_model as mm
+    o, bx = drive_carried(sc, times)
+    _, stale_by = stale_map(o, sc, bx)
+    w = sc.validators.weights
+    out = []
+    for head in (sc.ea, sc.eb):
+        right = merged_times_by_map(o, head.id, o.bi.by_creators)
+        assert right == o.merged(head.id)
+        stale = merged_times_by_map(o, head.id, stale_by)
+        for dflt in MT_DEFAULTS:
+            a, b = mm.median_time(right, w, dflt), mm.median_time(stale, w, dflt)
+            if a != b:
+                out.append((head.id, dflt, a, b))
+    return out
+
+
+_times = {}
+
+
+def times_of(name):
+    """The scenario's creation times: the first seed under which the medians
+    at ea and at eb both differ under the stale map (None if none of 64
+    does)."""
+    if name not in _times:
+        sc = get(name)
+        _times[name] = None
+        for seed in range(1, 65):
+            t = event_times(sc, seed)
+            heads = {d[0] for d in median_time_diffs(sc, t)}
+            if heads == {sc.ea.id, sc.eb.id}:
+                _times[name] = t
+                break
+    return _times[name]
+
+
+def observes_by_map(o, creators, head, x):
+    """x is head or an ancestor of it, from the oracle's rows (the rule of
+    lx_anc_observes): HighestBefore(head)[branch(x)].Seq >= seq(x), and where
+    head has detected the fork of the branch's creator -- marks are per
+    creator: the entry of the creator's original branch tells -- the
+    LowestAfter rule.  ``head`` is x or comes after it in Add order."""
+    if head.id == x.id:
+        return True
+    hb = o.get_highest_before(head.id)
+    b = o.get_event_branch_id(x.id)
+    if hb.is_fork_detected(creators[b]):
+        la = o.get_lowest_after(x.id).get(o.get_event_branch_id(head.id))
+        return 0 < la <= head.seq
+    ent = tuple(hb.get(b))
+    return ent != vo.FORK_DETECTED and ent[0] >= x.seq
+
+
+def ancestry_diffs(sc):
+    """[(head id, x id)] where the stale map changes observes(head, x); asserts
+    that the right map gives the ancestor sets of the parent lists."""
+    import ancestry_model as am
+    o, bx = drive_oracle(sc)
+    stale, _ = stale_map(o, sc, bx)
+    order = kept(sc)
+    m = am.Model(sc.validators, order)
+    out = []
+    for i, head in enumerate(order):
+        for j in range(i + 1):
+            right = observes_by_map(o, o.bi.creator_idxs, head, order[j])
+            assert right == m.observes(i, j), (head.id, order[j].id)
+            if observes_by_map(o, stale, head, order[j]) != right:
+                out.append((head.id, order[j].id))
+    return out
+
+
+def fork_evidence_diffs(sc):
+    """([(head id, creator, right, stale)], same with X's first seq): the
+    branch-interval rule of lx_anc_fork_pairs over the stale creator -> branches
+    map, and over the right map with the reused numbers' first seq taken from
+    X's fork branches; asserts that the right tables give the naive answer."""
+    import ancestry_model as am
+    import fork_evidence_model as fm
+    o, bx = drive_oracle(sc)
+    order = kept(sc)
+    m = am.Model(sc.validators, order)
+    br = fm.Branches(m)
+    cnt = fm.observed_counts(m, br)
+    marked = m.rows()[3]                                     # [head, branch]: the entry is a fork marker
+    right_of = {c: list(l) for c, l in br.of_creator.items()}
+    stale_of = {c: [b for b in l if b not in bx] for c, l in right_of.items()}
+    stale_of[sc.X] = sorted(stale_of.get(sc.X, []) + list(bx))
+    right_first = list(br.first)
+    stale_first = list(br.first)
+    for b, f in zip(bx, sc.fx):
+        stale_first[b] = f.seq
+    by_map, by_first = [], []
+    for h in range(len(sc.P), m.n):
+        naive = fm.evidence_row(m, h)
+        for c in range(sc.V):
+            br.of_creator, br.first = right_of, right_first
+            right = fm.interval_rule(br, cnt[h], c)
+            assert right == naive.get(c, fm.NO_EVIDENCE), (order[h].id, c)
+            if not marked[h, c]:                             # no fork of c detected: nothing is looked up
+                assert right == fm.NO_EVIDENCE
+                continue
+            br.of_creator = stale_of
+            stale = fm.interval_rule(br, cnt[h], c)
+            if stale != right:
+                by_map.append((order[h].id, c, right, stale))
+            br.of_creator, br.first = right_of, stale_first
+            try:
+                stale = fm.interval_rule(br, cnt[h], c)
+            except IndexError:                               # the pair's place lies outside the branch
+                stale = None
+            if stale != right:
+                by_first.append((order[h].id, c, right, stale))
+    br.of_creator, br.first = right_of, right_first
+    return by_map, by_first
+
+
+def cheaters_seen(sc, events, heads):
+    """{head id: set of creators} by the naive rule over ``events``."""
+    import ancestry_model as am
+    import fork_evidence_model as fm
+    m = am.Model(sc.validators, events)
+    at = {e.id: i for i, e in enumerate(events)}
+    return {h.id: set(fm.evidence_row(m, at[h.id])) for h in heads}
+
+
+def progress_epoch(sc):
+    """build_model.Epoch over P + A2 + T, all processed (Build of X's fork
+    event in between, as tests/test_gpu_refork.py drives it)."""
+    import build_model as bm
+    evs = [Event(e.id, e.creator, e.seq, e.lamport, e.parents, e.name) for e in kept(sc)]
+    ep = bm.Epoch(sc.validators, evs)
+    ep.advance(len(sc.P))
+    for f in sc.fx:
+        ep.flk.build(Event(f.id, f.creator, f.seq, f.lamport, f.parents, f.name))
+    ep.advance(len(evs))
+    return ep
+
+
+def progress_diffs(sc):
+    """[(event id, root id, right stake, stale stake)]: the pair stakes of
+    every processed event at its own frame (lx_abft_event_progress), counted
+    with the fork columns credited to X."""
+    import progress_model as pm
+    _, bx = drive_oracle(sc)
+    ep = progress_epoch(sc)
+    m = pm.ProgressModel(ep)
+    right = {e: m.event_pair_stakes(e, m.roots.get(int(m.frames[e]), [])) for e in range(m.n)}
+    for b in bx:
+        assert m.branch_creator[b] != sc.X
+        m.branch_creator[b] = sc.X
+    m._finish()
+    out = []
+    for e in range(m.n):
+        rs = m.roots.get(int(m.frames[e]), [])
+        for r, a, b in zip(rs, right[e], m.event_pair_stakes(e, rs)):
+            if a != b:
+                out.append((ep.events[e].id, ep.events[r].id, int(a), int(b)))
+    return out
+
+
+READERS = ("median_time", "ancestry", "fork_evidence", "progress")
+_reader_diffs = {}
+
+
+def reader_diffs(name):
+    """{reader: differing queries} of a variant (the abft readers on the
+    ``abft`` scenario of that name), computed once."""
+    if name not in _reader_diffs:
+        sc = get(name)
+        t = times_of(name)
+        _reader_diffs[name] = {
+            "median_time": median_time_diffs(sc, t) if t is not None else [],
+            "ancestry": ancestry_diffs(sc),
+            "fork_evidence": fork_evidence_diffs(sc)[0],
+            "progress": progress_diffs(get(name, abft=True)),
+        }
+    return _reader_diffs[name]
 
 
 # ---------------------------------------------------------------------------- reshuffled redo

@@ -19,7 +19,12 @@ was kept:
   refused at X's fork, then Y's fork;
 * column shards, G = 2 in one process, whole and incremental exchange, and
   through ShardedDagIndexer (two gloo ranks on one GPU);
-* a whole epoch rolled back at random points and redone in another order.
+* a whole epoch rolled back at random points and redone in another order,
+  with ancestry, fork evidence and MedianTime checked at every flush.
+
+The readers merged later (MedianTime, ancestry, fork evidence, Build without
+Add, frame progress) go through the same scenarios in
+tests/test_gpu_refork_readers.py.
 
 Before the index counted the generations of that map (lx_index::branch_gen)
 the QuorumIndexer, the abft engine and the shard exchange keyed their tables
@@ -38,8 +43,8 @@ drop.
 Measured on an MI355X: the module, 92 tests, 18.6 s in six processes (one
 per group); the first case of a process (which starts the device) 1.6-2.0 s,
 test_sharded_dag_indexer_after_refork (two more processes) 3.0 s,
-test_reshuffled_redo_epoch 0.5 s after the device start, every other case
-0.1 s or less.
+test_reshuffled_redo_epoch 0.5 s after the device start (also with the three
+readers checked at its 22 flushes), every other case 0.1 s or less.
 """
 
 import multiprocessing as mp
@@ -497,7 +502,12 @@ def test_sharded_dag_indexer_after_refork():
 
 def test_reshuffled_redo_epoch(lx):
     """Index, QuorumIndexer and shards over an epoch that is rolled back to the
-    last flush at random points and redone in another parents-first order."""
+    last flush at random points and redone in another parents-first order; at
+    every flush ancestry, fork evidence and MedianTime against their models
+    over the current order."""
+    import ancestry_model as am
+    import fork_evidence_model as fm
+    import median_time_model as mm
     validators, store, ops = rd.reshuffled()
     o = vo.Index()
     o.reset(validators, store.get)
@@ -507,9 +517,22 @@ def test_reshuffled_redo_epoch(lx):
     w = validators.weights
     oq = eo.QuorumIndexer(validators, o, eo.capped_metric(w, 2))
     gq = lx.emitter.QuorumIndexer(g, 2)
+    anc, mt = lx.AncestryIndex(g), lx.MedianTimeIndex(g)
+    times = dict(zip(sorted(store), mm.event_times(len(store), 9)))     # by event id, whatever the order
     me = 0
     for step, op in enumerate(ops):
         if op[0] == "flush":
+            order = [store[i] for i in g.ids]
+            m = am.Model(validators, order)
+            n = m.n
+            got = anc.observes_dense(np.repeat(np.arange(n), n), np.tile(np.arange(n), n)).reshape(n, n)
+            assert np.array_equal(got, m.observes_matrix()), step
+            assert anc.cheaters_dense(np.arange(n)) == [fm.cheaters(m, h) for h in range(n)], step
+            assert mt.num_times() == n
+            d = mm.derived_of(validators, order, [times[i] for i in g.ids])
+            for dflt in (0, 1 << 40):
+                want = [d.median(*d.merged(i)[:2], dflt) for i in range(n)]
+                assert [int(x) for x in mt.median_time(g.ids, dflt)] == want, (step, dflt)
             o.flush()
             g.flush()
             s.flush()
@@ -522,6 +545,7 @@ def test_reshuffled_redo_epoch(lx):
         part = op[1]
         add_all(o, g, part)
         s.add(part)
+        mt.set_times(part, [times[e.id] for e in part])      # (a drop forgets the times of what it drops)
         flags = [1 if validators.idxs[e.creator] == me else 0 for e in part]
         for e, fl in zip(part, flags):
             oq.process_event(e, bool(fl))
@@ -547,6 +571,9 @@ def test_reshuffled_redo_epoch(lx):
         assert list(map(int, gq.get_metrics_of(new))) == [oq.get_metric_of(x) for x in new], step
     for eid in g.ids:
         assert g.get_lowest_after(eid).to_bytes() == o.get_lowest_after(eid).to_bytes(), eid
+    assert any(fm.cheaters(m, h) for h in range(m.n))
     gq.close()
+    anc.close()
+    mt.close()
     g.ix.close()
     s.close()
