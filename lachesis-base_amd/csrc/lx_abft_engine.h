@@ -5,7 +5,7 @@
 //                         Build without Add and the progress rounds
 //   lx_abft_election.cpp  votes, elections ahead and round by round, blocks, the confirm sweep
 // Every device buffer, pinned buffer and event of the engine is owned by a type
-// that frees it (lx_devbuf.h, Event below): nothing is freed by hand.
+// that frees it (lx_devbuf.h): nothing is freed by hand.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -40,16 +40,7 @@ using BufPool = lxi::BlockPool<>;
 template <typename T>
 using DVec = lxi::PoolBuf<T>;
 
-struct Event {   // a HIP event, destroyed with its owner
-    hipEvent_t e = nullptr;
-    Event() = default;
-    Event(Event &&o) noexcept : e(o.e) { o.e = nullptr; }
-    Event &operator=(Event &&) = delete;
-    ~Event() {
-        if (e) (void)hipEventDestroy(e);
-    }
-    operator hipEvent_t() const { return e; }
-};
+using lxi::Event;   // lx_devbuf.h
 
 inline double now_ms() {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();

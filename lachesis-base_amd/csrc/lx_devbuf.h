@@ -255,6 +255,28 @@ public:
         return hipSuccess;
     }
 };
+
+struct Event {   // a HIP event, destroyed with its owner
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(Event &&o) noexcept : e(o.e) { o.e = nullptr; }
+    Event &operator=(Event &&) = delete;
+    ~Event() {
+        if (e) (void)hipEventDestroy(e);
+    }
+    operator hipEvent_t() const { return e; }
+};
+
+struct Stream {   // a HIP stream, destroyed with its owner (who waits for its work first)
+    hipStream_t s = nullptr;
+    Stream() = default;
+    Stream(Stream &&o) noexcept : s(o.s) { o.s = nullptr; }
+    Stream &operator=(Stream &&) = delete;
+    ~Stream() {
+        if (s) (void)hipStreamDestroy(s);
+    }
+    operator hipStream_t() const { return s; }
+};
 #endif
 
 }  // namespace lxi

@@ -37,8 +37,8 @@ struct lx_qi {
     lxi::DevBuf<unsigned long long> lastk;   // [V + 1] last batch position per creator / self (k_qi_mark)
     uint32_t gen = 0;
     std::vector<uint32_t> stage;           // host image of a large batch: events, then self flags
-    hipEvent_t staged = nullptr;           // its copy has read `stage`
-    hipEvent_t done = nullptr;             // the last ProcessEvent launch finished (freeing waits for it)
+    lxi::Event staged;                     // its copy has read `stage`
+    lxi::Event done;                       // the last ProcessEvent launch finished (freeing waits for it)
 
     int fail(int code, const char *fmt, ...) {
         char buf[512];
@@ -171,8 +171,6 @@ int lx_qi_create(lx_index *index, lx_qi **out) {
 void lx_qi_destroy(lx_qi *q) {
     if (!q) return;
     if (q->done) (void)hipEventSynchronize(q->done);   // ProcessEvent launches in flight
-    if (q->staged) (void)hipEventDestroy(q->staged);
-    if (q->done) (void)hipEventDestroy(q->done);
     delete q;
 }
 
@@ -236,7 +234,7 @@ int lx_qi_process_events(lx_qi *q, uint32_t n, const uint32_t *ev, const uint8_t
         }
     } else {
         QRC(ensure_cap(q, (uint64_t)2 * n, iv.stream));
-        if (!q->staged) QHIP(q, hipEventCreateWithFlags(&q->staged, hipEventDisableTiming));
+        if (!q->staged) QHIP(q, hipEventCreateWithFlags(&q->staged.e, hipEventDisableTiming));
         else QHIP(q, hipEventSynchronize(q->staged));
         q->stage.resize(2ull * n);
         for (uint32_t i = 0; i < n; i++) {
@@ -249,7 +247,7 @@ int lx_qi_process_events(lx_qi *q, uint32_t n, const uint32_t *ev, const uint8_t
         b.self = q->d_ev + n;
     }
     QHIP(q, lx::launch_qi_apply(qi_args(q, iv), b, iv.stream));
-    if (!q->done) QHIP(q, hipEventCreateWithFlags(&q->done, hipEventDisableTiming));
+    if (!q->done) QHIP(q, hipEventCreateWithFlags(&q->done.e, hipEventDisableTiming));
     QHIP(q, hipEventRecord(q->done, iv.stream));
     q->dirty = true;
     return 0;

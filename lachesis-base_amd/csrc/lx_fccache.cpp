@@ -60,8 +60,7 @@ struct FcCache {
     std::vector<uint32_t> dirty;
     std::vector<uint8_t> dmark;
     bool dirty_all = true;
-    MapBuf<uint8_t> M;   // [W][W], pinned and device-mapped: answers land here
-    uint8_t *M_dev = nullptr;                       // M as the device sees it
+    MappedBuf<uint8_t> M;   // [W][W], pinned and device-mapped: answers land here
     // the last fill: it writes row inflight_sa of M (a tile fill: every row)
     // while the host goes on as soon as its own answer landed; a row is reused
     // (cleared for a new occupant) only after that fill has finished.  A fill
@@ -69,7 +68,7 @@ struct FcCache {
     // entry carries the generation it was launched with; any other fill (a
     // refill of a row whose entries already match, a tile fill) by an event
     // recorded after it
-    hipEvent_t filled = nullptr;
+    Event filled;
     bool inflight = false;
     bool inflight_fresh = false;                    // the row was cleared for this fill: generations tell
     bool inflight_tile = false;
@@ -148,8 +147,8 @@ struct FcCache {
         // writing them any more
         if (inflight && (inflight_tile || s == inflight_sa || g7[s] == 1)) (void)fcc_quiesce(h, this);
         if (g7[s] == 1)   // the generation wrapped: entries of an old occupant could match again
-            for (uint32_t r = 0; r < W; r++) M[(uint64_t)r * W + s] = 0;
-        memset(M + (uint64_t)s * W, 0, W);
+            for (uint32_t r = 0; r < W; r++) M.host()[(uint64_t)r * W + s] = 0;
+        memset(M.host() + (uint64_t)s * W, 0, W);
         ref[s] = 1;
         return s;
     }
@@ -168,34 +167,26 @@ struct FcCache {
 
 namespace {
 
-void fcc_free(FcCache *c) {
-    if (!c) return;
-    if (c->filled) (void)hipEventDestroy(c->filled);
-    delete c;
-}
-
 int fcc_make(lx_index *h) {
     if (h->fcc) return 0;
     const uint32_t W = h->fcc_slots;
     FcCache *c = new FcCache();
     c->W = W;
     c->h = h;
-    void *d = nullptr;
     hipError_t e = c->evk.renew(W);
     if (e == hipSuccess) e = c->g7.renew(W);
     if (e == hipSuccess) e = c->evk_d.renew(W);
     if (e == hipSuccess) e = c->g7_d.renew(W);
-    if (e == hipSuccess) e = c->M.renew((uint64_t)W * W);
-    if (e == hipSuccess) { e = hipHostGetDevicePointer(&d, c->M, 0); c->M_dev = static_cast<uint8_t *>(d); }
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->filled, hipEventDisableTiming);
+    if (e == hipSuccess) e = c->M.grow((uint64_t)W * W, (uint64_t)W * W, nullptr, false);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->filled.e, hipEventDisableTiming);
     if (e == hipSuccess) e = c->d_rsum.renew(2ull * kAdd1PsumStride * W);
     if (e == hipSuccess) e = hipMemsetAsync(c->d_rsum, 0, 8ull * kAdd1PsumStride * W, h->stream);
     if (e != hipSuccess) {
-        fcc_free(c);
+        delete c;
         return h->hip(e, "ForklessCause cache (pinned memory)");
     }
     memset(c->g7, 0, W);
-    memset(c->M, 0, (uint64_t)W * W);
+    memset(c->M.host(), 0, (uint64_t)W * W);
     c->dmark.assign(W, 0);
     c->g7_launch.assign(W, 0);
     c->ev.assign(W, LX_NONE);
@@ -255,7 +246,7 @@ int fcc_sync_mirror(lx_index *h, FcCache *c) {
 // next miss (and its next a) while this fill still runs
 int fcc_row(lx_index *h, FcCache *c, uint32_t a, uint32_t sa) {
     FcArgs f;
-    int rc = lx_fc_args(h, c->used, c->evk_d, c->evk_d, c->M_dev + (uint64_t)sa * c->W, nullptr, &f);
+    int rc = lx_fc_args(h, c->used, c->evk_d, c->evk_d, c->M.dev() + (uint64_t)sa * c->W, nullptr, &f);
     if (rc) return rc;
     f.qa_bcast = 1;
     f.qa_imm = a;
@@ -290,7 +281,7 @@ int fcc_tile(lx_index *h, FcCache *c) {
     base.ev_branch = h->lay.ev_branch;
     const RootFcArgs r = lx::root_fc_step(base, c->evk_d, n, c->evk_d, n, c->evk[0], c->d_psum, words, sp);
     HIPCHK(h, lx::launch_root_fc(r, h->B > h->V, h->pack16 && h->max_seq <= 0xFFFFu, h->stream));
-    HIPCHK(h, lx::launch_fc_tile_out(c->d_psum, sp.n_split, n, rp, n, h->quorum, c->g7_d, c->M_dev, c->W, h->stream));
+    HIPCHK(h, lx::launch_fc_tile_out(c->d_psum, sp.n_split, n, rp, n, h->quorum, c->g7_d, c->M.dev(), c->W, h->stream));
     c->st.tile_fills++;
     c->st.pairs += (uint64_t)n * n;
     return 0;
@@ -304,7 +295,7 @@ int fcc_quiesce(lx_index *h, FcCache *c) {
     if (!c->inflight) return 0;
     const auto tq = std::chrono::steady_clock::now();
     if (!c->inflight_tile && c->inflight_fresh) {
-        const volatile uint8_t *row = c->M + (uint64_t)c->inflight_sa * c->W;
+        const volatile uint8_t *row = c->M.host() + (uint64_t)c->inflight_sa * c->W;
         const auto t0 = std::chrono::steady_clock::now();
         uint32_t s = 0;
         for (uint32_t k = 0; s < c->inflight_n; k++) {
@@ -332,7 +323,7 @@ int fcc_quiesce(lx_index *h, FcCache *c) {
 // synchronization (scripts/probes/sync_latency.hip); on timeout the stream is
 // synchronized, which also reports a failed launch
 int fcc_wait_answer(lx_index *h, FcCache *c, uint32_t sa, uint32_t sb) {
-    const volatile uint8_t *m = c->M + (uint64_t)sa * c->W + sb;
+    const volatile uint8_t *m = c->M.host() + (uint64_t)sa * c->W + sb;
     const uint8_t want = c->g7[sb];
     const auto t0 = std::chrono::steady_clock::now();
     for (uint32_t k = 0;; k++) {
@@ -349,7 +340,7 @@ inline bool fcc_hit(FcCache *c, uint32_t a, uint32_t b, uint8_t *out) {
     if (sa == LX_NONE) return false;
     const uint32_t sb = c->find(b);
     if (sb == LX_NONE) return false;
-    const uint8_t m = c->M[(uint64_t)sa * c->W + sb];
+    const uint8_t m = c->M.host()[(uint64_t)sa * c->W + sb];
     if ((m >> 1) != c->g7[sb]) return false;
     c->ref[sa] = c->ref[sb] = 1;
     c->last_a = a;
@@ -407,7 +398,7 @@ int fcc_query(lx_index *h, uint32_t a, uint32_t b, uint8_t *out) {
             d.ev[i] = c->evk[x];
             d.tag[i] = c->g7[x];
         }
-        rc = flush_add1_row(h, a, c->evk_d, c->used, c->g7_d, c->M_dev + (uint64_t)sa * c->W, c->d_rsum, &d);
+        rc = flush_add1_row(h, a, c->evk_d, c->used, c->g7_d, c->M.dev() + (uint64_t)sa * c->W, c->d_rsum, &d);
         if (rc == 0) {   // the kernel stores them into the mirror
             for (uint32_t x : c->dirty) c->dmark[x] = 0;
             c->dirty.clear();
@@ -442,7 +433,7 @@ int fcc_query(lx_index *h, uint32_t a, uint32_t b, uint8_t *out) {
     const auto t_end = std::chrono::steady_clock::now();
     c->st.miss_ns += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(t_end - t_miss).count();
     c->st.wait_ns += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(t_end - t_wait).count();
-    const uint8_t m = c->M[(uint64_t)sa * c->W + sb];
+    const uint8_t m = c->M.host()[(uint64_t)sa * c->W + sb];
     if ((m >> 1) != c->g7[sb]) return h->fail(LX_ERR_STATE, "ForklessCause cache: fill left (%u, %u) unanswered", a, b);
     c->ref[sa] = c->ref[sb] = 1;
     c->last_a = a;
@@ -455,7 +446,7 @@ int fcc_query(lx_index *h, uint32_t a, uint32_t b, uint8_t *out) {
 
 void fcc_destroy(lx_index *h) {
     if (h->fcc) (void)hipStreamSynchronize(h->stream);   // no fill in flight afterwards
-    fcc_free(h->fcc);
+    delete h->fcc;
     h->fcc = nullptr;
 }
 

@@ -1,6 +1,17 @@
-// lx_index.h -- the index handle behind the C ABI (include/lachesis_hip.h),
-// shared by the host engine (lx_capi.cpp) and the ForklessCause result cache
-// (lx_fccache.cpp).  Internal: not part of the ABI.
+// lx_index.h -- the index handle behind the C ABI (include/lachesis_hip.h) and
+// what the sources of the host engine share:
+//   lx_capi.cpp           create / destroy, options, Reset, Flush, DropNotFlushed, sync, stats, the index view
+//   lx_index_layout.cpp   growth and re-layout of the device buffers, column and cheater tables, argument builders
+//   lx_index_add.cpp      the big Add path (device arrays): batch preparation, the walks, the segmented walk
+//   lx_index_small.cpp    lx_add_batch and the small (latency) Add path: host mirror, staging slots, the pending run
+//   lx_index_fc.cpp       ForklessCause entry points, early-exit counters, the column-shard early exit
+//   lx_index_get.cpp      row getters and the resident row server
+//   lx_index_shard.cpp    the column-shard LowestAfter exchange, whole and incremental
+//   lx_index_persist.cpp  write-back, and the load from persisted tables (RLP: lx_rlp.h)
+// and their neighbours (lx_fccache.cpp, lx_rowseg.cpp, the abft engine through
+// the index view).  Every device buffer, pinned buffer, stream and event of the
+// handle is owned by a type that frees it (lx_devbuf.h): nothing is freed by
+// hand.  Internal: not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -96,7 +107,7 @@ struct Layout {
     // query scratch
     DU32 q_a, q_b;
     DBytes q_out;
-    // column-shard exchange cache (rows per shard at sc_events)
+    // column-shard exchange cache (rows per shard at sc.events)
     std::vector<DU32> sc_rows;
     std::vector<uint32_t> sc_nrows;
     DU32 sc_flag, sc_pos, sc_cols;
@@ -127,7 +138,13 @@ struct Layout {
 
 struct lx_index {
     int device = 0;
-    hipStream_t stream = nullptr;
+    // declared ahead of every buffer and event, so that it is destroyed last
+    // (after the buffers whose work ran on it; ~lx_index waits for that work)
+    lxi::Stream stream;
+    // the caller's stream of an entry point that takes one (null: the handle's)
+    hipStream_t stream_or(void *s) const { return s ? (hipStream_t)s : (hipStream_t)stream; }
+    lx_index() = default;
+    __attribute__((visibility("hidden"))) ~lx_index();   // lx_capi.cpp
     uint32_t shard_rank = 0, shard_count = 1;
     std::string err;
 
@@ -194,85 +211,108 @@ struct lx_index {
 
     bool b_crec_ok = false;                // lay.b_crec written (fork-free, 16-bit branches and seqs)
 
-    // column-shard exchange cache (lay.sc_*: rows per shard at sc_events)
-    uint64_t sc_events = ~0ull;
-    uint64_t sc_gen = 0;                  // branch_gen the rows were listed for
-    std::vector<uint32_t> sc_col_off;    // shard q's columns: sc_cols[sc_col_off[q] .. sc_col_off[q+1])
-    uint64_t sc_cols_gen = 0;             // branch_gen sc_cols was built for
+    // column-shard exchange cache (lay.sc_*: rows per shard at sc.events)
+    struct ShardCache {
+        uint64_t events = ~0ull;
+        uint64_t gen = 0;                 // branch_gen the rows were listed for
+        std::vector<uint32_t> col_off;    // shard q's columns: lay.sc_cols[col_off[q] .. col_off[q+1])
+        uint64_t cols_gen = 0;            // branch_gen lay.sc_cols was built for
+    } sc;
     // incremental LowestAfter exchange (lay.sx_*)
-    bool sx_full = true;                  // the next exchange sends whole blocks (reset, drop, load)
-    bool sx_active = false;               // pack / unpack / lx_shard_block use the dirty lists
-    std::vector<uint64_t> sx_roff;        // shard q's dirty rows: sx_rows[sx_roff[q] .. sx_roff[q + 1])
+    struct ShardDirty {
+        bool full = true;                 // the next exchange sends whole blocks (reset, drop, load)
+        bool active = false;              // pack / unpack / lx_shard_block use the dirty lists
+        std::vector<uint64_t> roff;       // shard q's dirty rows: lay.sx_rows[roff[q] .. roff[q + 1])
+    } sx;
 
     // write-back (lx_writeback_*, lay.wb_*)
-    bool wb_ready = false;
-    lx_writeback wb{};
-    std::string wb_bi;
+    struct WriteBack {
+        bool ready = false;               // `desc` and `bi` describe the index as it is
+        lx_writeback desc{};
+        std::string bi;                   // RLP(BranchesInfo)
+    } wb;
 
     // small-batch (latency) path, lx_small.hip: the host assigns branches in Add
     // order from a mirror of the per-event metadata and stages the batch in
     // pinned memory; one H2D copy + one launch, no sync
     uint32_t small_max = kSmallMaxN;       // option small_max: largest batch on this path (0: never)
-    bool hm_ok = false;                    // the mirror equals the device metadata
-    uint64_t hm_n = 0;                     // events whose (immutable) metadata the mirror holds
-    lxi::rawvec<uint32_t> hm_creator, hm_seq, hm_branch, hm_bbefore;
-    std::vector<uint32_t> hm_blen;         // per branch: events on it (= device branch_len)
-    std::vector<uint32_t> sm_level, sm_cnt, sm_touched;   // scratch
-    lxi::rawvec<uint2> sm_undo;            // add_batch_small: {branch, length before} per event
+    struct HostMirror {
+        bool ok = false;                   // the mirror equals the device metadata
+        uint64_t n = 0;                    // events whose (immutable) metadata the mirror holds
+        lxi::rawvec<uint32_t> creator, seq, branch, bbefore;
+        std::vector<uint32_t> blen;        // per branch: events on it (= device branch_len)
+    } hm;
+    struct SmallScratch {
+        std::vector<uint32_t> level, cnt, touched;
+        lxi::rawvec<uint2> undo;           // add_batch_small: {branch, length before} per event
+        SmallInlineArgs inl{};             // arguments of the last launch; images of <= kSmallInline words inline
+    } sm;
     // the pending run: small-path events assigned on the host but not launched
-    // yet, [pend_bs, pend_bs + pend_n), branches from pend_B0 (flush_pending)
-    uint32_t pend_n = 0, pend_B0 = 0, pend_maxlvl = 0;
-    uint64_t pend_bs = 0;
-    lxi::rawvec<SmallEv> pend_ev;          // records (q1.x = offset into pend_old, q2.w = h0 slot)
-    lxi::rawvec<uint32_t> pend_lvl;        // topological level inside the run
-    lxi::rawvec<uint2> pend_meta;          // per event {position | chunks << 16, chunk offset into pend_pl}
-    lxi::rawvec<uint16_t> pend_pl;         // in-run parents (run positions), chunks of 4 (k_small)
-    lxi::rawvec<uint2> pend_old;           // {target, global event}: parents older than the run, older prevs
-    uint64_t pend_npar = 0;                // parents of the run (LDS budget, small_fits)
-    uint32_t pend_nh = 0;                  // h0 slots of the run
-    std::vector<uint32_t> touch_mark;      // per branch: stamp of the last run that touched it
-    uint32_t touch_stamp = 0;
+    // yet, [pend.bs, pend.bs + pend.n), branches from pend.B0 (flush_pending)
+    struct PendingRun {
+        uint32_t n = 0, B0 = 0, maxlvl = 0;
+        uint64_t bs = 0;
+        lxi::rawvec<SmallEv> ev;           // records (q1.x = offset into old, q2.w = h0 slot)
+        lxi::rawvec<uint32_t> lvl;         // topological level inside the run
+        lxi::rawvec<uint2> meta;           // per event {position | chunks << 16, chunk offset into pl}
+        lxi::rawvec<uint16_t> pl;          // in-run parents (run positions), chunks of 4 (k_small)
+        lxi::rawvec<uint2> old;            // {target, global event}: parents older than the run, older prevs
+        uint64_t npar = 0;                 // parents of the run (LDS budget, small_fits)
+        uint32_t nh = 0;                   // h0 slots of the run
+    } pend;
+    struct Touched {
+        std::vector<uint32_t> mark;        // per branch: stamp of the last run that touched it
+        uint32_t stamp = 0;
+    } touch;
     // staging images in flight: slot k = a pinned image and its device copy,
     // copied by a kernel on the handle's stream (k_stage)
     static constexpr int kSlots = 4;
-    lxi::PinBuf<uint32_t> st_pin[kSlots];
-    hipEvent_t st_copied[kSlots] = {};     // the copy of slot k finished (its pinned image is free)
-    bool st_used[kSlots] = {};
-    uint32_t st_next = 0;
-    lxi::DU32 st_dev[kSlots];
-    SmallInlineArgs sm_inl{};              // arguments of the last launch; images of <= kSmallInline words inline
-    // restart from the persisted tables (lx_load_rows / lx_load_finish)
+    struct Staging {
+        lxi::PinBuf<uint32_t> pin[kSlots];
+        lxi::Event copied[kSlots];         // the copy of slot k finished (its pinned image is free)
+        bool used[kSlots] = {};
+        uint32_t next = 0;
+        lxi::DU32 dev[kSlots];
+    } st;
+    // restart from the persisted tables (lx_load_rows / lx_load_finish); `loading`
+    // stays flat: every entry point reads it (NOT_LOADING)
     bool loading = false;
-    std::vector<uint32_t> ld_first, ld_last, ld_count, ld_creator, ld_tail;   // per branch, as loaded
-    std::vector<uint32_t> ld_par;          // parents of every loaded event (dense)
-    std::vector<uint64_t> ld_poff;
-    uint32_t ld_B = 0;                     // branches seen so far (max ID + 1)
-    lxi::DBytes ld_buf;                    // device staging of a chunk's bytes and offsets
+    struct Load {
+        std::vector<uint32_t> first, last, count, creator, tail;   // per branch, as loaded
+        std::vector<uint32_t> par;         // parents of every loaded event (dense)
+        std::vector<uint64_t> poff;
+        uint32_t B = 0;                    // branches seen so far (max ID + 1)
+        lxi::DBytes buf;                   // device staging of a chunk's bytes and offsets
+    } ld;
 
     // pinned, device-mapped query buffers (per-call ForklessCause, getters)
-    lxi::MapBuf<uint8_t> qp;
-    uint8_t *qp_dev = nullptr;             // qp as the device sees it
-    uint32_t get_tag = 0;                  // completion tag of the last single-row getter
+    lxi::MappedBuf<uint8_t> qp;
+    // at least `bytes` of it (grown in steps of 64 KiB at least, after a wait for the stream)
+    int ensure_qp(uint64_t bytes) {
+        return hip(qp.grow(bytes, std::max<uint64_t>(bytes, 1u << 16), stream, true), "pinned query buffer");
+    }
     bool fc_unchecked = false;             // a ForklessCause launch may have flagged status[1] since lx_sync looked
     // the resident single-row server (k_get_server, option get_server)
     // 0 off; 1 auto: only while this handle is the process's only one (the
     // server holds a hardware queue while resident, and GPU_MAX_HW_QUEUES = 4
     // lets more streams share queues: work queued behind the resident kernel
     // would wait up to its 250-us idle exit); 2 on whatever the handle count
-    int srv_opt = 1;
-    hipStream_t srv_stream = nullptr;      // its own (high-priority) stream
-    lxi::MapBuf<uint64_t> srv_host;   // [0] request word, [1] exited gen
-    uint64_t *srv_dev = nullptr;           // srv_host as the device sees it
-    bool srv_live = false;                 // launched and not known to have left
-    uint32_t srv_gen = 0;
-    GetSrvArgs srv_args{};                 // the live server's arguments (ticks, seen0, gen aside)
-    uint64_t srv_ticks_us = 0;             // wall clock ticks per microsecond
-    uint64_t srv_served = 0, srv_launches = 0, srv_fallbacks = 0;
+    struct RowServer {
+        int opt = 1;
+        lxi::Stream stream;                // its own (high-priority) stream
+        lxi::MappedBuf<uint64_t> host;     // [0] request word, [1] exited gen
+        bool live = false;                 // launched and not known to have left
+        uint32_t gen = 0;
+        GetSrvArgs args{};                 // the live server's arguments (ticks, seen0, gen aside)
+        uint64_t ticks_us = 0;             // wall clock ticks per microsecond
+        uint64_t served = 0, launches = 0, fallbacks = 0;
+        uint32_t get_tag = 0;              // completion tag of the last single-row getter
+    } srv;
     uint32_t *q_sink = nullptr;            // status word the pinned FC path lets the kernel flag into
     bool get_host_check = true;            // option getter_host_check=0 (tests): device bound only
 
     // timing (HIP events on `stream`)
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    lxi::Event ev[4];
     lx_stats stats{};
     bool stats_lazy = false;               // small path: ms_index from ev[1..2] on demand
     bool small_timing = false;             // option timing=1: time small-path launches (two event records)
@@ -292,15 +332,17 @@ struct lx_index {
     uint32_t fc_early_lanes = 32;          // option fc_early_lanes: k_fc_early's lanes per query (16 or 32)
     lxi::DevBuf<unsigned long long> d_clk;     // walk clock records (IndexArgs::clk)
     // column-shard early exit (lx_fc_shard_undecided_dev): flags, scan, scan scratch
-    lxi::DU32 fcs_flag, fcs_pos;
-    lxi::DBytes fcs_tmp;
-    size_t fcs_tmp_bytes = 0;              // of it, what the scan asks for
+    struct ShardEarly {
+        lxi::DU32 flag, pos;
+        lxi::DBytes tmp;
+        size_t tmp_bytes = 0;              // of it, what the scan asks for
+    } fcs;
     lxi::DevBuf<unsigned long long> d_fc_full;   // early exit counters (device): past round 1, past round 2, all
     bool fc_early_forks = false;           // option fc_early_forks=1: the early exit in fork epochs too (k_fc_fk_early)
     lxi::DevBuf<unsigned long long> d_fc_fke;    // ... its counters, same layout
     bool seg_auto = true;                  // option seg_auto=0: never split a batch on its own
     uint32_t n_cus = 256;                  // compute units of the device (auto segments)
-    std::vector<hipEvent_t> seg_ev;
+    std::vector<lxi::Event> seg_ev;        // timing events of the segmented walks (seg_events)
     lx_seg_stats seg_stats{};
     // row-segment rank (options seg_rank / seg_count, lx_rowseg.cpp): one batch
     // per epoch, this rank walks and owns the rows of segment rs_rank
@@ -360,6 +402,19 @@ struct lx_index {
     } while (0)
 
 
+// Between lx_load_rows and lx_load_finish the branch table, B, the cheater
+// tables and the branch lengths are not rebuilt yet: every entry point that
+// reads or changes the epoch refuses (the load is finished or reset first).
+#define NOT_LOADING(h)                                                                            \
+    do {                                                                                          \
+        if ((h)->loading) return (h)->fail(LX_ERR_STATE, "index is loading (lx_load_finish first)"); \
+    } while (0)
+// entry points that read whole rows of any event: not on a row-segment rank
+#define WHOLE_INDEX(h)                                                                            \
+    do {                                                                                          \
+        if ((h)->rowseg()) return (h)->fail(LX_ERR_STATE, "needs a whole index (a row-segment rank holds its own rows)"); \
+    } while (0)
+
 // device scratch grown to `need` elements (contents not kept; waits for the stream before it frees)
 template <typename T>
 int grow_scratch(lx_index *h, lxi::DevBuf<T> &b, uint64_t need) {
@@ -369,10 +424,10 @@ int grow_scratch(lx_index *h, lxi::DevBuf<T> &b, uint64_t need) {
     return h->hip(b.renew(need), "grow_scratch");
 }
 
-// internal entry points shared by lx_capi.cpp and lx_fccache.cpp
+// internal entry points shared by lx_index_*.cpp, lx_capi.cpp and lx_fccache.cpp
 int lx_fc_args(lx_index *h, uint64_t n, const uint32_t *a, const uint32_t *b, uint8_t *out, uint32_t *partial,
-               FcArgs *fa);
-int flush_pending(lx_index *h);                 // launch the pending small-path run (lx_capi.cpp)
+               FcArgs *fa);                     // lx_index_fc.cpp
+int flush_pending(lx_index *h);                 // launch the pending small-path run (lx_index_small.cpp)
 // slots of the FC cache changed since its device mirror was written
 struct Add1Delta {
     uint32_t n;
@@ -383,7 +438,67 @@ int flush_add1_row(lx_index *h, uint32_t a, uint32_t *evk_dev, uint32_t n_slots,
                    uint32_t *psum_dev, const Add1Delta *delta);   // 1: not applicable
 int rs_begin(lx_index *h, IndexArgs ia, hipStream_t s);   // lx_rowseg.cpp
 int rs_planes(lx_index *h, uint32_t n);          // lx_rowseg.cpp: own rows of an n-event epoch
-void srv_stop(lx_index *h);   // lx_capi.cpp: the resident row server leaves
+void srv_stop(lx_index *h);   // lx_index_get.cpp: the resident row server leaves
 void fcc_destroy(lx_index *h);
 void fcc_clear(lx_index *h);                    // Reset: a new epoch
 void fcc_forget_from(lx_index *h, uint64_t n);  // DropNotFlushed: events >= n are gone
+
+// between the sources of the handle only (not exported)
+#pragma GCC visibility push(hidden)
+// lx_index_layout.cpp
+void free_all(lx_index *h);                     // a re-layout: every buffer of the old layout goes
+int grow_events(lx_index *h, uint64_t need);
+int grow_branches(lx_index *h, uint32_t need);
+int grow_scap(lx_index *h, uint32_t need);
+int grow_local(lx_index *h, uint32_t need);
+int ensure_batch(lx_index *h, uint64_t n, uint64_t npar);
+int rebuild_columns(lx_index *h);
+int la_tail(lx_index *h, hipStream_t s);
+int restart_tail(lx_index *h);                  // the LowestAfter tail table starts over
+BatchArgs batch_args(lx_index *h, uint32_t n, const uint32_t *creator, const uint32_t *seq, const uint32_t *poff,
+                     const uint32_t *par);
+IndexArgs index_args(const lx_index *h, uint32_t n, const uint32_t *poff, const uint32_t *par);
+UnfillArgs unfill_args(lx_index *h);
+// lx_index_add.cpp
+int add_batch_dev(lx_index *h, uint32_t n, const uint32_t *creator, const uint32_t *seq, const uint32_t *poff,
+                  const uint32_t *par, uint32_t *err_index);
+// lx_index_small.cpp
+int hm_sync(lx_index *h);
+// lx_index_shard.cpp
+void shard_bounds(const lx_index *h, uint32_t r, uint32_t *lo, uint32_t *hi);
+
+// Buffers that grow together, `guard` the one whose capacity the caller's check
+// reads: emptied first and allocated last, so that a failure on the way leaves
+// the check failing again
+template <typename G, typename... R>
+hipError_t renew_guarded(uint64_t cap, G &guard, R &...rest) {
+    guard.reset();
+    hipError_t e = hipSuccess;
+    (void)((e = rest.renew(cap)) || ...);
+    return e ? e : guard.renew(cap);
+}
+
+// the timing events of a segmented walk (lx_index_add.cpp, lx_rowseg.cpp)
+inline int seg_events(lx_index *h, size_t n) {
+    while (h->seg_ev.size() < n) {
+        lxi::Event e;
+        HIPCHK(h, hipEventCreate(&e.e));
+        h->seg_ev.push_back(std::move(e));
+    }
+    return 0;
+}
+#pragma GCC visibility pop
+
+// Host-time counters of the small Add path (make hprof: build_hprof/, read by
+// lx_host_prof; absent from the default build)
+#ifdef LX_HOST_PROF
+#include <x86intrin.h>
+extern uint64_t g_hprof[16];   // lx_index_small.cpp
+#define HP_T(v) const uint64_t v = __rdtsc()
+#define HP_ADD(k, t0) (g_hprof[k] += __rdtsc() - (t0))
+#define HP_CNT(k, x) (g_hprof[k] += (x))
+#else
+#define HP_T(v)
+#define HP_ADD(k, t0)
+#define HP_CNT(k, x)
+#endif

@@ -33,8 +33,7 @@ struct lx_mt {
     lxi::DevBuf<unsigned long long> times;  // [dense event]
     lxi::DevBuf<uint32_t> d_ev;             // a query's events (more than kMtInline)
     lxi::DevBuf<unsigned long long> d_rows; // merged rows of one launch
-    lxi::MapBuf<unsigned long long> med;    // medians of one launch, written by the kernel
-    unsigned long long *med_dev = nullptr;  // med as the device sees it
+    lxi::MappedBuf<unsigned long long> med;   // medians of one launch, written by the kernel
 
     int fail(int code, const char *fmt, ...) {
         char buf[512];
@@ -130,11 +129,8 @@ int query(lx_mt *m, uint32_t n, const uint32_t *ev, uint64_t default_time, uint6
             a.ev = m->d_ev;
         }
         if (median) {
-            if (m->med.cap() < c) {
-                MHIP(m, m->med.renew(std::max<uint64_t>(c, 256)));
-                MHIP(m, hipHostGetDevicePointer((void **)&m->med_dev, m->med.get(), 0));
-            }
-            a.median = m->med_dev;
+            MHIP(m, m->med.grow(c, std::max<uint64_t>(c, 256), nullptr, false));
+            a.median = m->med.dev();
         } else {
             MHIP(m, m->d_rows.grow((uint64_t)c * m->V));
             a.merged = m->d_rows;
@@ -144,7 +140,7 @@ int query(lx_mt *m, uint32_t n, const uint32_t *ev, uint64_t default_time, uint6
             MHIP(m, hipMemcpyAsync(merged + (uint64_t)lo * m->V, m->d_rows, (uint64_t)c * m->V * 8, hipMemcpyDeviceToHost,
                                    iv.stream));
         MHIP(m, hipStreamSynchronize(iv.stream));
-        if (median) memcpy(median + lo, m->med.get(), c * 8ull);
+        if (median) memcpy(median + lo, m->med.host(), c * 8ull);
     }
     return 0;
 }

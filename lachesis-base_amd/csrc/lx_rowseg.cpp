@@ -207,11 +207,7 @@ int rs_begin(lx_index *h, IndexArgs ia, hipStream_t s) {
         (rc = grow_scratch(h, h->lay.rs_lslot, (uint64_t)n)) ||
         (rc = grow_scratch(h, h->lay.rs_ctr, (uint64_t)2 + 2 * kMaxSegments)))
         return rc;
-    while (h->seg_ev.size() < 6) {
-        hipEvent_t e;
-        HIPCHK(h, hipEventCreate(&e));
-        h->seg_ev.push_back(e);
-    }
+    if ((rc = seg_events(h, 6))) return rc;
     h->rs_state = 0;
     // no LowestAfter row of another segment has been received in this epoch
     if ((rc = grow_scratch(h, h->lay.rs_stamp, (uint64_t)n))) return rc;

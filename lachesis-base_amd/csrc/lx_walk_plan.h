@@ -7,7 +7,7 @@
 // epoch and the options is here, as pure host functions: plain C++17, no HIP
 // types (tests/csrc/walk_plan_harness.cpp compiles it with g++ alone, and
 // tests/test_walk_plan_cpu.py checks it against a model of the rules).  The
-// callers (lx_capi.cpp, lx_rowseg.cpp) build one WalkPlan per batch;
+// callers (lx_index_add.cpp, lx_rowseg.cpp) build one WalkPlan per batch;
 // launch_index (lx_kernels.hip) maps it to the kernel and re-decides nothing.
 // A new walker variant is added in walk_variant() below and as one line of
 // launch_index's table.

@@ -268,3 +268,78 @@ def test_no_leak_across_handles(lx):
     assert free0 - free1 <= one
     assert probe.live_handles() == live0
     probe.close()
+
+
+LIFE_DAG = (4, 40, 2, 0, 0, 17)          # V = 4, two parents: 160 events
+LIFE_BIG = 128                           # the smallest batch option segments = 2 splits (64 events per segment)
+LX_ERR_ARG = -1
+
+
+def test_handles_destroyed_with_every_lazy_resource_alive(lx):
+    """Twenty handles created, driven and destroyed while each holds everything
+    a handle makes on demand: a staging slot and its event (a batch through the
+    walker), the segment events (option segments = 2), the resident row server
+    and its stream (get_server = 2), the ForklessCause cache (one cached pair),
+    the pinned query buffer (a per-call batch) and a pending small-path run.
+    Destroying a handle with work pending is ordinary use: lx_destroy waits for
+    it.  Device memory free after the twentieth cycle is not lower than after
+    the second by more than one cycle's footprint (one buffer leaked per cycle
+    would show eighteen times over), live_handles returns to its start after
+    every destroy, a refused lx_create leaves it alone, and every answer on
+    the way is the oracle's."""
+    import torch
+    n, ev, p, ch, fk, seed = LIFE_DAG
+    d = lx.tools.gen_dag(n, ev, p, ch, fk, seed)
+    w = [3, 2, 2, 1]
+    o = corc.OracleIndex(w)                                        # as the index is after the walker's batch
+    assert o.add_batch(*d.slice(0, LIFE_BIG)) == -1
+    qa, qb = lx.tools.fc_queries(d.lamport[:LIFE_BIG], 500, window=24, seed=seed)
+    fc_want = o.forkless_cause_batch(qa, qb)
+    pair = (LIFE_BIG - 1, 3)
+    pair_want = bool(o.forkless_cause_batch(np.array(pair[:1], np.uint32), np.array(pair[1:], np.uint32))[0])
+    hb_last, la_5 = o.hb(LIFE_BIG - 1), o.la(5)
+    assert o.add_batch(*d.slice(LIFE_BIG, LIFE_BIG + 1)) == -1
+    hb_small = o.hb(LIFE_BIG)
+    L = lx.load_library()
+    live0 = L.lx_live_handles()
+
+    with pytest.raises(lx.LxError) as refused:
+        lx.Index(shard_rank=2, shard_count=2)
+    assert refused.value.code == LX_ERR_ARG and L.lx_live_handles() == live0
+
+    def free():
+        torch.cuda.synchronize()
+        return torch.cuda.mem_get_info(0)[0]
+
+    def cycle(measure):
+        before = free() if measure else 0
+        ix = lx.Index(options={"small_max": 64, "segments": 2, "get_server": 2})
+        assert L.lx_live_handles() == live0 + 1
+        ix.reset(w)
+        ix.add_batch(*d.slice(0, LIFE_BIG))                        # the walker path, as two segments
+        assert ix.segment_stats()["segments"] == 2
+        assert ix.highest_before(LIFE_BIG - 1) == hb_last     # one row, through the row server
+        assert ix.lowest_after(5) == la_5
+        srv = ix.get_server_stats()
+        assert srv["launches"] >= 1 and srv["served"] >= 1
+        assert ix.forkless_cause(*pair) == pair_want               # the result cache
+        assert ix.forkless_cause(*pair) == pair_want and ix.fc_cache_stats()["hits"] >= 1
+        np.testing.assert_array_equal(ix.forkless_cause_batch(qa, qb), fc_want)   # the pinned query buffer
+        ix.add_batch(*d.slice(LIFE_BIG, LIFE_BIG + 1))             # the small path: pending until something reads
+        assert ix.highest_before(LIFE_BIG) == hb_small
+        ix.add_batch(*d.slice(LIFE_BIG + 1, LIFE_BIG + 2))         # ... and this one still is at the destroy
+        assert ix.num_events() == LIFE_BIG + 2
+        alive = free() if measure else 0
+        ix.close()
+        assert L.lx_live_handles() == live0
+        return before - alive
+
+    cycle(False)
+    footprint = cycle(True)
+    free2 = free()
+    for _ in range(18):
+        cycle(False)
+    free20 = free()
+    print("LIFECYCLE footprint %d B, free after cycle 2 %d, after cycle 20 %d" % (footprint, free2, free20))
+    assert footprint > 0
+    assert free2 - free20 <= footprint

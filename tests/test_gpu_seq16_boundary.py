@@ -34,7 +34,7 @@ is kept; cpw=12,crec=1 is among the variants because compact records are off
 by default.
 
 What the cases catch was tried once with a library whose gates in
-lx_fccache.cpp:328 and lx_capi.cpp:2875 read 0x1FFFF (k_root_fc16 and the
+lx_fccache.cpp:283 and lx_index_shard.cpp:112 read 0x1FFFF (k_root_fc16 and the
 uint16 wire past 16 bits, both read-only on their inputs):
 test_per_pair_fc_across_boundary and test_shard_wire_changes_width failed,
 test_abft_root_pairs_per_pair_fc did not -- the truncated compare is only
